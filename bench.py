@@ -7,12 +7,16 @@ MFMA) followed by the rasterization of every sample's P = 262,146 per-pixel Gaus
 the reference's sampler calls once per denoising step (gaussian_diffusion.py:350 -> denoiser.py:284-287).
 value = renders / s = B * 4 * n_gpus / t_step, inputs resident in HBM, synthetic data, random-init weights.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps (all of them replays of the captured step) and prints the contract line.
+`--dump-outputs DIR` then also writes what the last timed step returned (DIR/<name>.npy, float32).  Everything informational below,
+and the roofline events inside the timed region, is measured only with `--full`.
 
 With N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (torch.distributed.run, 127.0.0.1, one
 per GPU, RCCL); launched BY torch.distributed.run (the driver's way) it reads RANK / LOCAL_RANK / WORLD_SIZE.
 
-Prints ONE JSON line (rank 0).  Extra objects next to the contract keys:
+Prints ONE JSON line (rank 0).  Extra objects next to the contract keys (`--full` only):
   roofline      dominant DiT kernel, HIP events on the launch stream inside the timed region; `traffic` from the PMC passes of
                 tools/pmc_traffic.py IF they were taken on exactly these kernel sources (else null)
   raster        the rasterizer on its HBM and fp32-VALU rooflines, forward and forward+backward, in the regime the step renders
@@ -108,6 +112,29 @@ def pmc_traffic(family):
         return None
     except Exception:
         return None
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+GAUSSIAN_ATTRS = ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity")     # what GaussianModel.set_data keeps
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: the arrays of the last timed step as DIR/<name>.npy, float32.  Should they hold more than 64 MB together
+    (large --batch / --res), each is replaced by the same fraction of its elements, flattened, at positions drawn with a fixed seed:
+    two builds given the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in arrays.items()}
+    budget = DUMP_LIMIT_BYTES - 1024 * len(arrays)               # room for the .npy headers
+    total = sum(v.nbytes for v in arrays.values())
+    rng = np.random.default_rng(0)
+    for name in sorted(arrays):
+        v = arrays[name]
+        if total > budget:
+            flat = v.reshape(-1)
+            v = flat[np.sort(rng.choice(flat.size, flat.size * budget // total, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return sorted(arrays)
 
 
 def respawn(a):
@@ -532,13 +559,20 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="create the process group and issue every barrier / all-reduce even for a world of one "
                     "(the one-GPU RCCL smoke run: same init, streams and collective calls as N > 1)")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("DGS_GRAPH", "1")), help="1 (default): the timed steps are replays of DGSDenoiser.forward captured as ONE hipGraph "
-                    "(dgs_amd/graph.py), except the steps that carry the roofline kernel's HIP events (every 4th), which are enqueued eagerly; 0: every step eager")
+                    "(dgs_amd/graph.py), except, with --full, the steps that carry the roofline kernel's HIP events (every 4th), which are enqueued eagerly; 0: every step eager")
     ap.add_argument("--preheat-s", type=float, default=1.0, help="seconds of the same step run (untimed) before the warm-up steps: a timed region of "
                     "~0.15 s that starts from idle clocks measures the DVFS ramp, not the kernels (BENCH_r03 vs the builder's runs: -8 %%)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no informational objects, only the timed region and its roofline")
     ap.add_argument("--extras-timeout", type=float, default=420.0, help="seconds the informational objects may take before the line is printed without them")
+    ap.add_argument("--full", action="store_true", help="also measure everything informational: the roofline kernel's events inside the timed "
+                    "region, the sampling loop, step variants, kernel families, raster roofline, batch sweep, scene-512, training steps, CPU "
+                    "baseline (--no-extras / --no-cpu-baseline leave parts out); without it a run times the contract step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned (rank 0): "
+                    "rendered.npy [B, V, 3, H, W] and gaussians_<b>_<attribute>.npy per sample, float32, 64 MB at most")
     a = ap.parse_args()
+    if a.dump_outputs and a.mode != "infer":
+        ap.error("--dump-outputs writes the outputs of the inference step (--mode infer)")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn(a)
@@ -581,8 +615,9 @@ def main():
         assert int(seen.item()) == world, f"all-reduce over the process group counted {int(seen.item())} ranks, WORLD_SIZE={world}"
     assert world == a.gpus, f"--gpus {a.gpus} but WORLD_SIZE={world}"
     dry_note = {"dry_run": "CPU emulator + gloo + tiny model: exercises launch / timing / reduction plumbing, NOT a measurement"} if a.dry_run_cpu else {}
+    extras = a.full and not a.no_extras     # the informational objects (a dry run never has them)
 
-    if a.mode == "train-scene":      # BASELINE configs[4] as the timed region (profiling runs; the default line carries it as `train_step_scene_512`)
+    if a.mode == "train-scene":      # BASELINE configs[4] as the timed region (profiling runs; the --full line carries it as `train_step_scene_512`)
         tb = scene_train_bench(a, dev, rank, world, a.steps, a.warmup)
         if rank == 0:
             print(json.dumps({
@@ -630,7 +665,7 @@ def main():
 
     from dgs_amd.dit import DitOps
     clock = {}
-    if not a.dry_run_cpu:
+    if a.full and not a.dry_run_cpu:
         clock["at_start_mhz"] = round(DitOps().shader_clock_mhz(dev), 0)      # before any load: the idle / ramping state
 
     use_graph = bool(a.graph) and not a.dry_run_cpu
@@ -673,10 +708,11 @@ def main():
             for _ in range(10):
                 (graph_step or step)()
             _sync()
-        clock["after_preheat_mhz"] = round(DitOps().shader_clock_mhz(dev), 0)
+        if a.full:
+            clock["after_preheat_mhz"] = round(DitOps().shader_clock_mhz(dev), 0)
 
     loop_ms = None
-    if not a.no_extras:
+    if extras:
         # Informational: the reference's 30-step sampling loop end to end -- DGSDenoiser.forward + the device
         # sampler step (dgs_amd/sampler.py) per iteration; one untimed loop, one timed.  Not part of `value`.
         from dgs_amd import sampler as sm
@@ -694,7 +730,7 @@ def main():
                 loop_ms = (time.perf_counter() - l0) * 1e3
 
     variants = None
-    if not a.no_extras and not a.dry_run_cpu:
+    if extras and not a.dry_run_cpu:
         # the step both ways, 20 steps each, untimed region: what the graph buys on this box, and how far the host runs ahead
         variants = {}
         for name, fn in (("eager", step), ("graph", graph_step)):
@@ -706,7 +742,7 @@ def main():
             variants[name] = {"ms_per_step": round(wall, 3), "host_enqueue_ms_per_step": round(host, 3), "gpu_ms_per_step": round(gpu, 3)}
 
     families = None
-    if not a.no_extras and not a.dry_run_cpu and B == 1:
+    if extras and not a.dry_run_cpu and B == 1:
         # every kernel family of the block on its own roofline (informational; two eager steps per family with HIP events around its
         # launches, outside the timed region): MFMA for attention and the K-heavy GEMMs, HBM for LayerNorm; the gate-residual family
         # (proj + fc2) moves the fp32 residual stream and is priced on both
@@ -744,10 +780,10 @@ def main():
         run_step()
     nl = MODEL_CFG["num_layers"]
     per_step = {"attention": nl, "gemm_qkv": nl, "gemm_gate_residual": 2 * nl, "gemm_fc1_gelu": nl, "layernorm": 2 * nl, "gemm_proj": nl, "gemm_fc2": nl}[a.roofline_kernel]
-    # HIP events around every launch of the roofline kernel on every 4th step of the timed region: an event record is a packet
+    # --full: HIP events around every launch of the roofline kernel on every 4th step of the timed region: an event record is a packet
     # of its own between two kernels (~2 us), 48 of them per step were 1.5 % of the step they measure.  Those steps are enqueued
     # eagerly (events cannot be re-armed inside a captured graph); the others are graph replays
-    prof_steps = [] if a.dry_run_cpu else [i for i in range(a.steps) if i % 4 == 0]
+    prof_steps = [i for i in range(a.steps) if i % 4 == 0] if a.full and not a.dry_run_cpu else []
     events = {i: [torch.cuda.Event(enable_timing=True) for _ in range(2 * per_step)] for i in prof_steps}
     for ev in events.values():  # materialise the HIP event handles before the timed region
         for e in ev:
@@ -777,11 +813,16 @@ def main():
         # the last step's outputs are the captured graph's own tensors: keep copies for the PSNR check behind the informational objects
         # (the graph is dropped there to free its memory)
         rendered = rendered.clone()
-        g0_ = gaussians[0]
-        gaussians = [types.SimpleNamespace(_xyz=g0_._xyz.clone(), _features_dc=g0_._features_dc.clone(), _scaling=g0_._scaling.clone(),
-                                           _rotation=g0_._rotation.clone(), _opacity=g0_._opacity.clone())]
-    if not a.dry_run_cpu:
+        gaussians = [types.SimpleNamespace(**{n: getattr(g, n).clone() for n in GAUSSIAN_ATTRS if getattr(g, n, None) is not None}) for g in gaussians]
+    if a.full and not a.dry_run_cpu:
         clock["after_timed_region_mhz"] = round(DitOps().shader_clock_mhz(dev), 0)
+    if a.dump_outputs and rank == 0:
+        # what DGSDenoiser.forward returned in the last timed step: the renders and every sample's GaussianModel tensors
+        arrays = {"rendered": rendered}
+        for b, g in enumerate(gaussians):
+            arrays.update({f"gaussians_{b}{n}": getattr(g, n) for n in GAUSSIAN_ATTRS if getattr(g, n, None) is not None})
+        names = dump_outputs(a.dump_outputs, arrays)
+        print(f"[bench] wrote {len(names)} arrays to {a.dump_outputs}", file=sys.stderr, flush=True)
     rank_ms = [local_ms]
     if DIST["on"]:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -795,13 +836,6 @@ def main():
     if rank == 0:
         ms = elapsed / a.steps * 1e3
         value = B * V * world / (elapsed / a.steps)
-        kern_ms = [events[i][2 * j].elapsed_time(events[i][2 * j + 1]) for i in prof_steps for j in range(per_step)]
-        avg_s = float(np.mean(kern_ms)) * 1e-3 if kern_ms else float("inf")
-        achieved = kernel_flops(a.roofline_kernel, L, B) / avg_s / 1e12
-        traffic = pmc_traffic("dit")
-        tr_bytes = None
-        if traffic and B == 1 and res == 256 and V == 4:
-            tr_bytes = traffic.get("dit", {}).get(a.roofline_kernel, {}).get("traffic_bytes_per_launch")
         out = {
             "metric": "novel-view renders/sec (DiT step + GS raster) at 256^2", "value": round(value, 2), "unit": "renders/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
@@ -811,10 +845,6 @@ def main():
                                    f"rasterizations of P={2 + V * res * res} Gaussians at {res}^2 per sample; random-init weights",
                        "batch_per_gpu": B, "views": V, "resolution": res, "tokens": L, "gaussians": 2 + V * res * res,
                        "dit_tflop_per_sample": round(dit_flops(L, MODEL_CFG["width"], nl) / 1e12, 3), "parallelism": f"dp{world}"},
-            "roofline": {"kernel": a.roofline_kernel, "bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_BF16_MFMA / 1e12,
-                         "unit": "TFLOP/s", "frac": round(achieved * 1e12 / PEAK_BF16_MFMA, 4), "traffic": tr_bytes,
-                         "launches_timed": len(kern_ms), "avg_launch_us": round(avg_s * 1e6, 2),
-                         "step_frac_of_peak": round(dit_flops(L, MODEL_CFG["width"], nl) * B / (ms * 1e-3) / PEAK_BF16_MFMA, 4)},
             # what the timed region looked like from the host and from the device (rank 0): `host_enqueue_ms` = until the last step
             # was enqueued (the host runs ahead of the device by ms_per_step - this), `gpu_ms` = between two events on the stream,
             # `shader_clock_mhz` = s_memtime / s_memrealtime of a probe kernel at three moments, `per_rank_ms` = every rank's own time
@@ -826,6 +856,18 @@ def main():
                              "ranks_seen": len(rank_ms)},
             **dry_note,
         }
+        if a.full:
+            kern_ms = [events[i][2 * j].elapsed_time(events[i][2 * j + 1]) for i in prof_steps for j in range(per_step)]
+            avg_s = float(np.mean(kern_ms)) * 1e-3 if kern_ms else float("inf")
+            achieved = kernel_flops(a.roofline_kernel, L, B) / avg_s / 1e12
+            traffic = pmc_traffic("dit")
+            tr_bytes = None
+            if traffic and B == 1 and res == 256 and V == 4:
+                tr_bytes = traffic.get("dit", {}).get(a.roofline_kernel, {}).get("traffic_bytes_per_launch")
+            out["roofline"] = {"kernel": a.roofline_kernel, "bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_BF16_MFMA / 1e12,
+                               "unit": "TFLOP/s", "frac": round(achieved * 1e12 / PEAK_BF16_MFMA, 4), "traffic": tr_bytes,
+                               "launches_timed": len(kern_ms), "avg_launch_us": round(avg_s * 1e6, 2),
+                               "step_frac_of_peak": round(dit_flops(L, MODEL_CFG["width"], nl) * B / (ms * 1e-3) / PEAK_BF16_MFMA, 4)}
         if variants:
             out["step_variants"] = variants
         if families:
@@ -847,7 +889,7 @@ def main():
     watchdog.start()
     x0 = time.perf_counter()
     stage = lambda name: print(f"[bench] {name} ({time.perf_counter() - x0:.1f} s)", file=sys.stderr, flush=True) if rank == 0 else None
-    if not a.no_extras:
+    if extras:
         try:
             stage("extras: raster roofline")
             rr = raster_roofline(dev, res, V) if rank == 0 else None
@@ -877,7 +919,7 @@ def main():
             out["train_step_scene_512"] = tb512
             out["extras_s"] = round(time.perf_counter() - x0, 1)       # wall time of the informational objects above
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline and not a.no_extras:
+        if world == 1 and a.full and not a.no_cpu_baseline and not a.no_extras:
             model = dn.DGSDenoiser(dict(width=1024, in_channels=9, patch_size=8, num_layers=24, ray_pe_type="relative_plk"), device=dev)
             model.reset_parameters(seed=0)
             final = {k: getattr(gaussians[0], "_" + n)[None] for k, n in

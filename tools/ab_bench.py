@@ -14,7 +14,7 @@ for var in variants:
             k, v = kv.split("=")
             env[k] = v
     for kern in kernels:
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--no-cpu-baseline",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline",
                               "--roofline-kernel", kern], env=env, capture_output=True, text=True).stdout.strip().splitlines()
         d = json.loads(out[-1])
         print(var, kern, "ms/step", d["ms_per_step"], "kernel us", d["roofline"]["avg_launch_us"], "TF", d["roofline"]["achieved"], flush=True)

@@ -10,7 +10,7 @@ cd $R
 export PYTHONPATH=$R/open-diffusiongs_amd:$R
 rm -f $out/kg_spread_ab.txt
 for rep in 1 2 3 4; do for lib in libdgs_hip.so libdgs_hip_var.so; do
-  DGS_AMD_LIBRARY=$R/open-diffusiongs_amd/lib/$lib python bench.py --steps 40 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python -c "
+  DGS_AMD_LIBRARY=$R/open-diffusiongs_amd/lib/$lib python bench.py --full --steps 40 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$lib rep $rep ms/step', d['ms_per_step'], 'attention us', d['roofline']['avg_launch_us'])" >> $out/kg_spread_ab.txt

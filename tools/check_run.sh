@@ -11,5 +11,5 @@ timeout 400 python -m pytest tests/test_smoke_c1.py -m gpu -q 2>&1 | tail -6 > $
 cat $out/${tag}_c1_gpu.txt
 timeout 600 python -m pytest tests -m gpu -q 2>&1 | tail -6 > $out/${tag}_pytest_gpu.txt
 cat $out/${tag}_pytest_gpu.txt
-timeout 400 python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout 400 python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 cut -c1-400 $out/${tag}_bench.json

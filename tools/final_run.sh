@@ -11,7 +11,7 @@ timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $out/${tag}_pytes
 python __graft_entry__.py --smoke > $out/${tag}_smoke.txt 2>&1
 # the contract bench before the profiler / PMC passes
 # (`roofline.traffic` then comes from the profiles/pmc_traffic.json of the previous call: null if the kernel sources changed since)
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -c 600 $out/${tag}_pytest_gpu.txt; tail -2 $out/${tag}_smoke.txt; cut -c1-600 $out/${tag}_bench.json
 prof() {   # name, command...
     local name=$1; shift
@@ -34,9 +34,9 @@ tools/ubench/exp_ulp_bench > $out/${tag}_exp_ulp_final.txt 2>&1
 # the training step under the driver's launch line with forced (world-1 RCCL) collectives: host lead in the backward, verify-wait split
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --mode train --steps 4 --warmup 2 --force-dist --no-cpu-baseline > $out/${tag}_train_rccl_world1.json 2>> $out/${tag}_bench.err
 # the driver's multi-GPU launch line with the one GPU there is: RCCL process group of one rank, every collective issued
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 2 --force-dist --no-cpu-baseline > $out/${tag}_bench_torchrun_rccl_world1.json 2>> $out/${tag}_bench.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 2 --force-dist --full --no-cpu-baseline > $out/${tag}_bench_torchrun_rccl_world1.json 2>> $out/${tag}_bench.err
 cut -c1-400 $out/${tag}_bench_torchrun_rccl_world1.json
 # second contract line, now with `traffic` (the PMC JSON above carries this tree's source hashes)
 cp gpurun_out/pmc_traffic.json profiles/pmc_traffic.json
-python bench.py --no-extras --no-cpu-baseline > $out/${tag}_bench_after_pmc.json 2>> $out/${tag}_bench.err
+python bench.py --full --no-extras --no-cpu-baseline > $out/${tag}_bench_after_pmc.json 2>> $out/${tag}_bench.err
 cut -c1-900 $out/${tag}_bench_after_pmc.json
