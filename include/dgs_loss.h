@@ -6,8 +6,9 @@
  *     psnr = -10 * log10(l2_loss)                                                                           :303
  *     compute_psnr: clamp both to [0, 1] first                                                               :399-402
  * and the autograd backward of the lambda_mse term (d/d rendering = 2 (rendering - target) * grad_scale / n).
- * LPIPS (a VGG network) and SSIM are out of scope.  One pass over the images, per-sample sums reduced in a fixed order
- * (deterministic), no host synchronisation.  Device pointers; returns DGS_OK or a negative DgsStatus.
+ * and the SSIM term (`SsimLoss`, :216-234; evaluated over all b * v views on every step, :317-321): DgsSsimArgs below.
+ * LPIPS (a VGG network that needs weights) is out of scope; its input path is DgsResizeArgs.  One pass over the images, per-sample
+ * sums reduced in a fixed order (deterministic), no host synchronisation.  Device pointers; returns DGS_OK or a negative DgsStatus.
  */
 #ifndef DGS_LOSS_H
 #define DGS_LOSS_H
@@ -79,6 +80,39 @@ typedef struct DgsPointsLossArgs {
 
 int64_t dgs_points_loss_workspace_floats(int32_t B, int32_t V);
 int dgs_points_loss(const DgsPointsLossArgs* args, dgs_stream_t stream);
+
+/* SSIM of the reference's SsimLoss (losses.py:216-234: pytorch_msssim.SSIM(win_size=11, win_sigma=1.5, data_range=1.0,
+ * size_average=False, channel=3)), forward and backward with respect to x, fused with the MSE term (csrc/ssim.hip):
+ *     w[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0 .. 10, normalised to sum 1 (fp32);  G = separable VALID filter with w along H, then W
+ *     mu1 = G(x), mu2 = G(y), s1 = G(x x) - mu1^2, s2 = G(y y) - mu2^2, s12 = G(x y) - mu1 mu2,  C1 = (0.01 R)^2, C2 = (0.03 R)^2
+ *     m = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * (2 s12 + C2) / (s1 + s2 + C2);   ssim[n] = mean of m over C (H - 10) (W - 10)
+ * dgs_ssim: one tiled launch (no moment map goes to memory; with `saved` the three partial-derivative maps of the backward are
+ * written) + one finishing launch that adds the tile sums in index order.  With `l2` it also emits dgs_mse_psnr's per-sample
+ * l2 / psnr of (x, y) (clamp01 = 0), samples being groups of V = N / B consecutive images.
+ * dgs_ssim_backward: one launch, a gather over `saved` (no atomics):
+ *     dx = g[n] * d ssim[n] / d x  +  mse_scale[b] * 2 (x - y) / (V C H W)
+ * Same inputs, same bits.  H < 11 or W < 11 (or N * C > 65535 planes in one call): DGS_ERR_INVALID_ARGUMENT. */
+typedef struct DgsSsimArgs {
+    int32_t N, C, H, W;        /* images, channels, plane size                                              */
+    int32_t B;                 /* samples: N = B * V (a divisor of N; only the MSE outputs / mse_scale use it) */
+    const float* x;            /* f32 [N, C, H, W]: the renderings (differentiated)                          */
+    const float* y;            /* f32 [N, C, H, W]: the targets                                              */
+    float data_range;          /* R: 1.0 in the reference                                                    */
+    float* ssim;               /* forward out f32 [N]                                                        */
+    float* l2;                 /* forward optional out f32 [B]: mean squared error per sample                */
+    float* psnr;               /* forward optional out f32 [B]: -10 log10(l2) (needs l2)                      */
+    float* saved;              /* f32 [dgs_ssim_saved_floats(N, C, H, W)], layout private to the library: written by the forward
+                                  when given, REQUIRED by the backward                                      */
+    float* workspace;          /* forward: f32 [dgs_ssim_workspace_floats(N, C, H, W)]                        */
+    const float* g;            /* backward: f32 [N], d L / d ssim[n]                                          */
+    const float* mse_scale;    /* backward optional f32 [B]: d L / d l2[b]                                    */
+    float* dx;                 /* backward out f32 [N, C, H, W]                                               */
+} DgsSsimArgs;
+
+int64_t dgs_ssim_workspace_floats(int32_t N, int32_t C, int32_t H, int32_t W);
+int64_t dgs_ssim_saved_floats(int32_t N, int32_t C, int32_t H, int32_t W);
+int dgs_ssim(const DgsSsimArgs* args, dgs_stream_t stream);
+int dgs_ssim_backward(const DgsSsimArgs* args, dgs_stream_t stream);
 
 #ifdef __cplusplus
 }

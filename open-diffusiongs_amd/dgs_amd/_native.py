@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # or an A/B side (tools/ab_build.sh).  Never a fallback: whatever is named must exist and pass the ABI check.
 LIB_PATH = os.environ.get("DGS_AMD_LIBRARY") or os.path.join(os.path.dirname(HERE), "lib", "libdgs_hip.so")
 
-ABI_VERSION = 8          # == DGS_ABI_VERSION of include/dgs_raster.h; bump both whenever a struct or prototype changes
+ABI_VERSION = 9          # == DGS_ABI_VERSION of include/dgs_raster.h; bump both whenever a struct or prototype changes
 DGS_ERR_BINNING_OVERFLOW = -7    # include/dgs_raster.h DgsStatus
 c_float_p = ctypes.POINTER(ctypes.c_float)
 ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
@@ -368,7 +368,15 @@ class DgsPointsLossArgs(ctypes.Structure):
                 ("workspace", ctypes.c_void_p)]
 
 
-LOSS_SYMBOLS = ["dgs_mse_psnr", "dgs_resize_bilinear", "dgs_resize_bilinear_backward", "dgs_points_loss", "dgs_points_loss_workspace_floats"]
+class DgsSsimArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("B", ctypes.c_int32),
+                ("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("data_range", ctypes.c_float), ("ssim", ctypes.c_void_p),
+                ("l2", ctypes.c_void_p), ("psnr", ctypes.c_void_p), ("saved", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("g", ctypes.c_void_p), ("mse_scale", ctypes.c_void_p), ("dx", ctypes.c_void_p)]
+
+
+LOSS_SYMBOLS = ["dgs_mse_psnr", "dgs_resize_bilinear", "dgs_resize_bilinear_backward", "dgs_points_loss", "dgs_points_loss_workspace_floats",
+                "dgs_ssim", "dgs_ssim_backward", "dgs_ssim_workspace_floats", "dgs_ssim_saved_floats"]
 
 
 def _declare_loss(L):
@@ -381,6 +389,12 @@ def _declare_loss(L):
     L.dgs_points_loss.argtypes = [ctypes.POINTER(DgsPointsLossArgs), ctypes.c_void_p]
     L.dgs_points_loss_workspace_floats.restype = ctypes.c_int64
     L.dgs_points_loss_workspace_floats.argtypes = [ctypes.c_int32, ctypes.c_int32]
+    for fn in (L.dgs_ssim, L.dgs_ssim_backward):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(DgsSsimArgs), ctypes.c_void_p]
+    for fn in (L.dgs_ssim_workspace_floats, L.dgs_ssim_saved_floats):
+        fn.restype = ctypes.c_int64
+        fn.argtypes = [ctypes.c_int32] * 4
     return L
 
 

@@ -1,9 +1,11 @@
-"""Loss consumers on the device: per-sample MSE + PSNR and the MSE gradient in one pass, the LPIPS
-input resize, and the two terms on the denoiser's pixel-aligned points (points-distribution and xyz loss) with their gradient.
+"""Loss consumers on the device: per-sample MSE + PSNR and the MSE gradient in one pass, the SSIM
+term fused with them, the LPIPS input resize, and the two terms on the denoiser's pixel-aligned points (points-distribution and xyz
+loss) with their gradient.
 
 Mirrors diffusionGS/utils/losses.py: the `l2_loss` / `psnr` terms of LossComputer.forward (:281-285, :303), `compute_psnr`
-(:399-402), `l2_loss_xyz` (:288-292) and `pointsdist_loss` (:325-364).  LPIPS / SSIM (network-based) are out of scope.
-csrc/loss.hip through include/dgs_loss.h; no CPU fallback."""
+(:399-402), `SsimLoss` (:216-234, :317-321), `l2_loss_xyz` (:288-292) and `pointsdist_loss` (:325-364).  The LPIPS network (VGG,
+needs weights) is out of scope; so is MetricComputer.compute_ssim (:428-463), skimage's operator, a different one.
+csrc/loss.hip and csrc/ssim.hip through include/dgs_loss.h; no CPU fallback."""
 import ctypes
 
 import torch
@@ -154,3 +156,148 @@ def points_losses(img_aligned_xyz, ray_o, gt_img_aligned_xyz=None, masks=None, l
     w.r.t. `img_aligned_xyz` [b, v, 3, h, w] (the statistics of the points-distribution target are detached, as in the reference).
     `masks` [b, v, 1, h, w] is the reference's `masks_input`."""
     return _PointsLoss.apply(img_aligned_xyz, ray_o, gt_img_aligned_xyz, masks, lib)
+
+
+SSIM_WINDOW = 11
+
+
+def _ssim_views(x, y):
+    """[N, C, H, W] or [b, v, C, H, W] -> contiguous f32 [N, C, H, W] pair and the number of samples b (N for 4-d input)."""
+    if x.shape != y.shape or x.dim() not in (4, 5):
+        raise ValueError(f"ssim: expected two [N, C, H, W] or [b, v, C, H, W] tensors of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError("ssim: float32 tensors expected")
+    if x.shape[-2] < SSIM_WINDOW or x.shape[-1] < SSIM_WINDOW:
+        raise ValueError(f"ssim: planes of {x.shape[-2]} x {x.shape[-1]} are smaller than the {SSIM_WINDOW}-tap window")
+    samples = x.shape[0]
+    return x.reshape(-1, *x.shape[-3:]).contiguous(), y.reshape(-1, *y.shape[-3:]).contiguous(), samples
+
+
+def _ssim_args(x, y, samples, data_range, saved):
+    a = _native.DgsSsimArgs()
+    a.N, a.C, a.H, a.W = (int(d) for d in x.shape)
+    a.B, a.data_range = int(samples), float(data_range)
+    a.x, a.y, a.saved = ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(saved.data_ptr()) if saved is not None else None
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream) if x.is_cuda else None
+    return a, stream
+
+
+def _ssim_forward(x, y, samples, data_range, want_mse, want_saved, lib):
+    L = lib or _native.lib()
+    N, C, H, W = x.shape
+    dev = x.device
+    new = lambda n: torch.empty(int(n), dtype=torch.float32, device=dev)
+    saved = new(L.dgs_ssim_saved_floats(N, C, H, W)) if want_saved else None
+    out, ws = new(N), new(L.dgs_ssim_workspace_floats(N, C, H, W))
+    l2, psnr = (new(samples), new(samples)) if want_mse else (None, None)
+    a, stream = _ssim_args(x, y, samples, data_range, saved)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    a.ssim, a.l2, a.psnr, a.workspace = ptr(out), ptr(l2), ptr(psnr), ptr(ws)
+    rc = L.dgs_ssim(ctypes.byref(a), stream)
+    if rc != 0:
+        raise RuntimeError(f"dgs_ssim failed: {rc}")
+    return out, l2, psnr, saved
+
+
+def _ssim_backward(x, y, samples, data_range, saved, g, mse_scale, lib):
+    L = lib or _native.lib()
+    dx = torch.empty_like(x)
+    g = g.contiguous().float()                                       # no copies when they already are f32 and dense
+    mse_scale = mse_scale.contiguous().float() if mse_scale is not None else None
+    a, stream = _ssim_args(x, y, samples, data_range, saved)
+    a.g, a.dx = ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(dx.data_ptr())
+    a.mse_scale = ctypes.c_void_p(mse_scale.data_ptr()) if mse_scale is not None else None
+    rc = L.dgs_ssim_backward(ctypes.byref(a), stream)
+    if rc != 0:
+        raise RuntimeError(f"dgs_ssim_backward failed: {rc}")
+    return dx
+
+
+class _Ssim(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, data_range, lib):
+        xs, ys, _ = _ssim_views(x, y)
+        need = ctx.needs_input_grad[0]
+        out, _, _, saved = _ssim_forward(xs, ys, xs.shape[0], data_range, False, need, lib)
+        if need:
+            ctx.save_for_backward(xs, ys, saved)
+        ctx.meta = (tuple(x.shape), data_range, lib)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xs, ys, saved = ctx.saved_tensors
+        shape, data_range, lib = ctx.meta
+        return _ssim_backward(xs, ys, xs.shape[0], data_range, saved, g, None, lib).reshape(shape), None, None, None
+
+
+def ssim(x, y, data_range=1.0, lib=None):
+    """pytorch_msssim.SSIM(win_size=11, win_sigma=1.5, data_range, size_average=False) of `x` against `y` ([N, C, H, W] or
+    [b, v, C, H, W], float32) -> [N] (N = b * v), differentiable in `x`.  One fused launch each way (csrc/ssim.hip)."""
+    return _Ssim.apply(x, y, float(data_range), lib)
+
+
+def ssim_loss(rendering, target, lib=None):
+    """losses.py:317-321: `(1 - ssim).reshape(b, v).mean(dim=1)` for rendering / target [b, v, 3, h, w] -> [b]."""
+    if rendering.dim() != 5:
+        raise ValueError("ssim_loss: [b, v, C, h, w] tensors expected")
+    b, v = rendering.shape[:2]
+    return (1.0 - ssim(rendering, target, 1.0, lib)).reshape(b, v).mean(dim=1)
+
+
+_coef_cache = {}
+
+
+def _coefs(key, values, dev):
+    """A small constant vector on the device, built once per (shape, weights, device)."""
+    k = (key, values, str(dev))
+    if k not in _coef_cache:
+        _coef_cache[k] = torch.tensor(values, dtype=torch.float32, device=dev)
+    return _coef_cache[k]
+
+
+class _ImageLosses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rendering, target, lambda_mse, lambda_ssim, lib):
+        xs, ys, b = _ssim_views(rendering, target)
+        v = xs.shape[0] // b
+        need = ctx.needs_input_grad[0]
+        s, l2, psnr, saved = _ssim_forward(xs, ys, b, 1.0, True, need, lib)
+        sl = (1.0 - s).reshape(b, v).mean(dim=1)                     # the reference's expression (ssim_loss above)
+        # lambda_mse * l2.mean() + lambda_ssim * sl.mean() as one dot product with a constant vector
+        loss = torch.dot(torch.cat([l2, sl]), _coefs("fwd", (lambda_mse / b,) * b + (lambda_ssim / b,) * b, xs.device))
+        if need:
+            ctx.save_for_backward(xs, ys, saved)
+        ctx.meta = (tuple(rendering.shape), b, v, lambda_mse, lambda_ssim, lib)
+        ctx.mark_non_differentiable(psnr)
+        ctx.set_materialize_grads(False)
+        return loss, l2, psnr, sl
+
+    @staticmethod
+    def backward(ctx, g_loss, g_l2, _g_psnr, g_sl):
+        xs, ys, saved = ctx.saved_tensors
+        shape, b, v, lambda_mse, lambda_ssim, lib = ctx.meta
+        dev = xs.device
+        # d / d l2[b] and d / d ssim[n] of whatever was built on the outputs, folded into the one backward launch: [b] weights of the
+        # squared-error sums followed by [N] weights of the images' ssim (d ssim_loss[b] / d ssim[n] = -1 / v)
+        n = b * v
+        if g_loss is not None:
+            w = g_loss.reshape(1) * _coefs("bwd", (lambda_mse / b,) * b + (-lambda_ssim / n,) * n, dev)
+        else:
+            w = torch.zeros(b + n, dtype=torch.float32, device=dev)
+        if g_l2 is not None:
+            w[:b] += g_l2
+        if g_sl is not None:
+            w[b:] -= (g_sl * (1.0 / v)).repeat_interleave(v)
+        return _ssim_backward(xs, ys, b, 1.0, saved, w[b:], w[:b], lib).reshape(shape), None, None, None, None
+
+
+def image_losses(rendering, target, lambda_mse=1.0, lambda_ssim=0.0, lib=None):
+    """rendering / target [b, v, C, h, w] -> (loss, l2 [b], psnr [b], ssim_loss [b]) with
+    loss = lambda_mse * l2.mean() + lambda_ssim * ssim_loss.mean() (how PointDiffusionSystem combines the two image terms,
+    systems/diffusion_gs_system.py:94-128).  One autograd node: the forward is dgs_ssim (the squared-error sums ride along), the
+    backward ONE dgs_ssim_backward launch that writes d loss / d rendering of both terms in a single store.  loss, l2 and
+    ssim_loss are differentiable w.r.t. `rendering`."""
+    if rendering.dim() != 5:
+        raise ValueError("image_losses: [b, v, C, h, w] tensors expected")
+    return _ImageLosses.apply(rendering, target, float(lambda_mse), float(lambda_ssim), lib)

@@ -1,9 +1,10 @@
 """One data-parallel training step of the hot path (what PointDiffusionSystem.training_step does around the model,
-systems/diffusion_gs_system.py:71-128, minus the parts that are out of scope: noise schedule, LPIPS, logging):
+systems/diffusion_gs_system.py:71-128, minus the parts that are out of scope: noise schedule, the LPIPS network, logging):
 
     gaussians = model.image_to_gaussians(noisy views)          DiT forward, activations saved / per-block recompute   (HIP)
     renders   = model.render_gaussians(gaussians, cameras)     all b*v views, one launch sequence                     (HIP)
     loss      = mean((renders - target)^2)                     the reference's lambda_mse term                        (HIP: dgs_amd.losses)
+                [+ lambda_ssim * mean(1 - ssim(renders, target))   with DataParallelTrainer(lambda_ssim=...): one fused loss node]
     loss.backward()                                            rasterizer backward + DiT backward                     (HIP)
       `- per finished gradient group: all-reduce of the buckets it completes, on RCCL's stream, WHILE the backward of the
          earlier blocks is still being enqueued / executed                                                           (dgs_amd.parallel)
@@ -28,7 +29,7 @@ class DataParallelTrainer:
     block) hands the model back: a later plain `loss.backward()` then returns gradients through autograd again."""
 
     def __init__(self, model, optimizer, bucket_bytes=None, accumulate_grad_batches=1, group=None, compress=None, force_collectives=False,
-                 max_grad_norm=None, broadcast_from=0, deterministic=None):
+                 max_grad_norm=None, broadcast_from=0, deterministic=None, lambda_ssim=None):
         """deterministic (default on; DGS_RASTER_DETERMINISTIC=0 or False turns it off): the rasterizer backward without floating-point
         atomics (dgs_raster.h `scratch`), which makes the WHOLE step bit-reproducible -- the DiT backward, the bucketed all-reduce
         order, the norm and the AdamW launch already are -- for +0.10 of 1.07 ms of rasterizer backward at 4 views of 256^2
@@ -40,7 +41,10 @@ class DataParallelTrainer:
         max_grad_norm: global-norm gradient clip (Lightning `gradient_clip_val`; the reference trains with 0.5,
         configs/diffusionGS_rel.yaml:76-77) -- the norm's partial sums are taken bucket by bucket behind each bucket's all-reduce and
         the scale is applied inside the optimizer launch (FusedAdamW) or as one in-place scale of the flat buffer (any other optimizer).
-        broadcast_from: the rank whose parameters every rank starts from (DDP's init-time broadcast); None skips it."""
+        broadcast_from: the rank whose parameters every rank starts from (DDP's init-time broadcast); None skips it.
+        lambda_ssim: None (default) trains on the MSE term through losses.mse_psnr, as before.  A float -- 0.0 included: the reference
+        evaluates and logs the term at weight 0 -- routes the step through losses.image_losses (loss = l2.mean() + lambda_ssim *
+        ssim_loss.mean(), one fused backward launch) and keeps the per-sample term in `last_ssim_loss`."""
         self.model, self.opt = model, optimizer
         import os
         if deterministic is None:
@@ -85,7 +89,9 @@ class DataParallelTrainer:
         model._grads_in_place = True
         model._block_hook = self._on_gradients_final
         self._attach_grads()
+        self.lambda_ssim = None if lambda_ssim is None else float(lambda_ssim)
         self.last_psnr = None
+        self.last_ssim_loss = None       # [b] of the last micro-batch when lambda_ssim is set
         self.lead_probe = None           # a list: every block_done callback appends (stage, host time, event recorded on the compute stream)
 
     def close(self):
@@ -173,7 +179,12 @@ class DataParallelTrainer:
             self._last_micro = j == K - 1
             params, _ = m.image_to_gaussians(batch["image"][sl], batch["ray_o"][sl], batch["ray_d"][sl], t[sl])
             rendered = m.render_gaussians(params, c2w[sl], k[sl], H, W)
-            loss, _l2, self.last_psnr = losses.mse_psnr(rendered, target[sl].to(rendered.dtype), lib=getattr(m, "_lib", None))
+            if self.lambda_ssim is None:
+                loss, _l2, self.last_psnr = losses.mse_psnr(rendered, target[sl].to(rendered.dtype), lib=getattr(m, "_lib", None))
+            else:
+                loss, _l2, self.last_psnr, ssim_term = losses.image_losses(rendered, target[sl].to(rendered.dtype), 1.0, self.lambda_ssim,
+                                                                            lib=getattr(m, "_lib", None))
+                self.last_ssim_loss = ssim_term.detach()
             (loss * (1.0 / (K * self.world))).backward()       # mean over micro-batches and ranks folded into the scale
             total = total + loss.detach()
             if not self._last_micro:
