@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # or an A/B side (tools/ab_build.sh).  Never a fallback: whatever is named must exist and pass the ABI check.
 LIB_PATH = os.environ.get("DGS_AMD_LIBRARY") or os.path.join(os.path.dirname(HERE), "lib", "libdgs_hip.so")
 
-ABI_VERSION = 9          # == DGS_ABI_VERSION of include/dgs_raster.h; bump both whenever a struct or prototype changes
+ABI_VERSION = 10         # == DGS_ABI_VERSION of include/dgs_raster.h; bump both whenever a struct or prototype changes
 DGS_ERR_BINNING_OVERFLOW = -7    # include/dgs_raster.h DgsStatus
 c_float_p = ctypes.POINTER(ctypes.c_float)
 ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
@@ -430,8 +430,27 @@ def _declare_optim(L):
     return L
 
 
+class DgsFieldArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("R", ctypes.c_int32), ("nb", ctypes.c_int32), ("split", ctypes.c_int32),
+                ("xyz", ctypes.c_void_p), ("scaling", ctypes.c_void_p), ("rotation", ctypes.c_void_p), ("opacity", ctypes.c_void_p),
+                ("mesh_scale", ctypes.c_float), ("scaling_modifier", ctypes.c_float), ("lin", ctypes.c_void_p), ("lo", ctypes.c_void_p),
+                ("hi", ctypes.c_void_p), ("occ", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64)]
+
+
+# every symbol include/dgs_field.h declares (checked by tests/test_field.py)
+FIELD_SYMBOLS = ["dgs_gaussian_field", "dgs_gaussian_field_workspace_bytes"]
+
+
+def _declare_field(L):
+    L.dgs_gaussian_field.restype = ctypes.c_int
+    L.dgs_gaussian_field.argtypes = [ctypes.POINTER(DgsFieldArgs), ctypes.c_void_p]
+    L.dgs_gaussian_field_workspace_bytes.restype = ctypes.c_int64
+    L.dgs_gaussian_field_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
+    return L
+
+
 _declare_raster = _declare
 
 
-def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss prototypes on one library)
-    return _declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L)))))
+def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field prototypes on one library)
+    return _declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L))))))

@@ -7,9 +7,12 @@ Mirrors diffusionGS/models/gsrenderer/gs_core.py:
     render_generic                             :1300-1316   (same, for caller-supplied cameras; [v, h, w, 3] uint8)
     GaussianModel.construct_dtypes / save_ply / load_ply   :578-760   (the layout 3DGS viewers read: x y z, red green blue,
                                                              f_dc_*, f_rest_* padded to SH degree 3, opacity, scale_*, rot_*)
+    GaussianModel.extract_fields               :786-852     (reference: a host loop over num_blocks^3 blocks, ~15 torch ops and a
+                                                             synchronisation each; here one C call, csrc/field.hip)
 The reference writes / reads the file through the `plyfile` package (binary_little_endian 1.0, one "vertex" element, scalar
 properties in dtype order); that byte layout is restated here with numpy structured arrays -- no extra dependency.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -159,3 +162,58 @@ def load_ply(pc, path, device="cpu"):
     rots = np.stack([v[n] for n in idx("rot_")], axis=1)
     t = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float32, device=device)
     return pc.set_data(t(xyz), t(feats).transpose(1, 2).contiguous(), t(scales), t(rots), t(v["opacity"][:, None]))
+
+
+def field_tables(resolution, num_blocks, relax_ratio=1.5):
+    """The grid of gs_core.py:809-824, on the host in fp32 with the reference's own expressions: lin [R] = linspace(-1, 1, R), and per
+    block index the exclusive bounds lo / hi [nb] of a member's coordinate (the chunk's first / last coordinate -/+ block_size *
+    relax_ratio).  A tensor minus a Python scalar is one fp32 operation on the rounded scalar, as `vmin -= ...` is."""
+    block_size = 2 / num_blocks
+    lin = torch.linspace(-1, 1, resolution)
+    chunks = lin.split(resolution // num_blocks)
+    lo = torch.stack([c.min() for c in chunks]) - block_size * relax_ratio
+    hi = torch.stack([c.max() for c in chunks]) + block_size * relax_ratio
+    return lin, lo, hi
+
+
+def extract_fields(pc, resolution=128, num_blocks=16, relax_ratio=1.5, lib=None):
+    """gs_core.py:786-852: `pc` a GaussianModel -> occ [R, R, R] float32 on its device, indexed [x, y, z]; sets pc.mesh_center
+    (tensor [3]) and pc.mesh_scale (float) as the reference does.  One call of dgs_gaussian_field (include/dgs_field.h) on the
+    current stream; membership in a block is decided by comparing the fp32 numbers formed here with the reference's expressions."""
+    from . import _native
+    block_size = 2 / num_blocks
+    assert resolution % block_size == 0
+    if resolution % num_blocks != 0:
+        raise ValueError(f"extract_fields: resolution {resolution} is not a multiple of num_blocks {num_blocks}")
+    with torch.no_grad():
+        xyz = pc.get_xyz.float()
+        if xyz.shape[0] == 0:
+            raise ValueError("extract_fields: no Gaussians (all filtered away?)")
+        mn, mx = xyz.amin(0), xyz.amax(0)
+        pc.mesh_center = (mn + mx) / 2
+        pc.mesh_scale = 1.8 / (mx - mn).amax().item()
+        dev = xyz.device
+        xyzs = ((xyz - pc.mesh_center) * pc.mesh_scale).contiguous()
+        lin, lo, hi = (t.to(dev).contiguous() for t in field_tables(resolution, num_blocks, relax_ratio))
+        scaling, rotation, opacity = (t.detach().float().contiguous() for t in (pc._scaling, pc._rotation, pc._opacity))
+        occ = torch.empty([resolution] * 3, dtype=torch.float32, device=dev)
+        L = lib or _native.lib()
+        a = _native.DgsFieldArgs()
+        a.N, a.R, a.nb, a.split = xyz.shape[0], resolution, num_blocks, resolution // num_blocks
+        a.mesh_scale = pc.mesh_scale
+        a.scaling_modifier = 1.0 if pc.scaling_modifier is None else float(pc.scaling_modifier)
+        a.workspace_bytes = L.dgs_gaussian_field_workspace_bytes(a.N, a.nb)
+        if a.workspace_bytes <= 0:
+            raise ValueError(f"extract_fields: unsupported grid (num_blocks {num_blocks})")
+        ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=dev)
+        a.xyz, a.scaling, a.rotation, a.opacity, a.lin, a.lo, a.hi, a.occ, a.workspace = (
+            ctypes.c_void_p(t.data_ptr()) for t in (xyzs, scaling, rotation, opacity, lin, lo, hi, occ, ws))
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if xyz.is_cuda else None
+        rc = L.dgs_gaussian_field(ctypes.byref(a), stream)
+        if rc != 0:
+            raise ValueError(f"dgs_gaussian_field failed: {rc} ({_native.status_string(L, rc)})") if rc == -1 else RuntimeError(
+                f"dgs_gaussian_field failed: {rc} ({_native.status_string(L, rc)})")
+        if xyz.is_cuda:
+            for t in (xyzs, scaling, rotation, opacity, lin, lo, hi, ws):
+                t.record_stream(torch.cuda.current_stream(dev))
+    return occ

@@ -44,7 +44,8 @@ class AttrDict(dict):
 
 
 class GaussianModel:
-    """Container + activations of gs_core.py:321-373,544-570 (exp / normalize / sigmoid)."""
+    """Container + activations of gs_core.py:321-373,544-570 (exp / normalize / sigmoid), the filters of :376-496 (torch expressions
+    on the raw parameters, in place, returning self) and the density field of :786-852 (csrc/field.hip)."""
 
     def __init__(self, sh_degree, scaling_modifier=None):
         self.sh_degree, self.scaling_modifier = sh_degree, scaling_modifier
@@ -81,6 +82,71 @@ class GaussianModel:
     @property
     def get_features(self):
         return self._features_dc if self._features_rest is None else torch.cat((self._features_dc, self._features_rest), dim=1)
+
+    def get_covariance(self, scaling_modifier=1):
+        """gs_core.py:572-575, 112-147, 324-328: the six upper-triangle entries of (R S)(R S)^T, [N, 6]."""
+        q = self._rotation / torch.sqrt((self._rotation * self._rotation).sum(dim=1))[:, None]
+        r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+        R = torch.stack((1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                         2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                         2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)), dim=1).reshape(-1, 3, 3)
+        L = R @ torch.diag_embed(scaling_modifier * self.get_scaling)
+        cov = L @ L.transpose(1, 2)
+        return torch.stack((cov[:, 0, 0], cov[:, 0, 1], cov[:, 0, 2], cov[:, 1, 1], cov[:, 1, 2], cov[:, 2, 2]), dim=1)
+
+    # -- filters, gs_core.py:376-496: masks are torch expressions on the raw tensors (bit-identical with the reference's) --
+    def to(self, device):
+        self._xyz, self._features_dc = self._xyz.to(device), self._features_dc.to(device)
+        if self.sh_degree > 0:
+            self._features_rest = self._features_rest.to(device)
+        self._scaling, self._rotation, self._opacity = self._scaling.to(device), self._rotation.to(device), self._opacity.to(device)
+        return self
+
+    def filter(self, valid_mask):
+        self._xyz, self._features_dc = self._xyz[valid_mask], self._features_dc[valid_mask]
+        if self.sh_degree > 0:
+            self._features_rest = self._features_rest[valid_mask]
+        self._scaling, self._rotation, self._opacity = self._scaling[valid_mask], self._rotation[valid_mask], self._opacity[valid_mask]
+        return self
+
+    def crop(self, crop_bbx=[-1, 1, -1, 1, -1, 1]):
+        x_min, x_max, y_min, y_max, z_min, z_max = crop_bbx
+        xyz = self._xyz
+        invalid = ((xyz[:, 0] < x_min) | (xyz[:, 0] > x_max) | (xyz[:, 1] < y_min) | (xyz[:, 1] > y_max)
+                   | (xyz[:, 2] < z_min) | (xyz[:, 2] > z_max))
+        return self.filter(~invalid)
+
+    def prune(self, opacity_thres=0.05):
+        return self.filter(self.get_opacity.squeeze(1) > opacity_thres)
+
+    def prune_by_nearfar(self, cam_origins, nearfar_percent=(0.01, 0.99)):
+        assert len(nearfar_percent) == 2
+        assert nearfar_percent[0] < nearfar_percent[1]
+        assert nearfar_percent[0] >= 0 and nearfar_percent[1] <= 1
+        device = self._xyz.device
+        dists = torch.cdist(self._xyz[None], cam_origins[None].to(device))[0]                       # [points, cameras]
+        pct = torch.quantile(dists, torch.tensor(nearfar_percent).to(device), dim=0)                 # [2, cameras]
+        reject = ((dists < pct[0:1, :]) | (dists > pct[1:2, :])).any(dim=1)
+        return self.filter(~reject)
+
+    def apply_all_filters(self, opacity_thres=0.05, crop_bbx=[-1, 1, -1, 1, -1, 1], cam_origins=None, nearfar_percent=(0.005, 1.0)):
+        self.prune(opacity_thres)
+        if crop_bbx is not None:
+            self.crop(crop_bbx)
+        if cam_origins is not None:
+            self.prune_by_nearfar(cam_origins, nearfar_percent)
+        return self
+
+    def shrink_bbx(self, drop_ratio=0.05):
+        xyz = self._xyz
+        xyz_min, xyz_max = torch.quantile(xyz, torch.tensor([drop_ratio, 1 - drop_ratio]).float().to(xyz.device), dim=0)
+        xyz_min, xyz_max = xyz_min.detach().cpu().numpy(), xyz_max.detach().cpu().numpy()
+        return self.crop([xyz_min[0], xyz_max[0], xyz_min[1], xyz_max[1], xyz_min[2], xyz_max[2]])
+
+    def extract_fields(self, resolution=128, num_blocks=16, relax_ratio=1.5, lib=None):
+        """gs_core.py:786-852 -> occ [R, R, R]; sets self.mesh_center / self.mesh_scale (dgs_amd/consumers.py, csrc/field.hip)."""
+        from . import consumers
+        return consumers.extract_fields(self, resolution, num_blocks, relax_ratio, lib)
 
     # -- on-disk format, gs_core.py:578-760 (dgs_amd/consumers.py) --
     def construct_dtypes(self, use_fp16=False, enable_gs_viewer=True):
