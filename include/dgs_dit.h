@@ -314,8 +314,11 @@ typedef struct DgsDitBackwardArgs {
 
 /* recompute: 0 / 1 as DgsDitForwardArgs.train_recompute */
 size_t dgs_dit_saved_bytes(const DgsDitModel* m, int32_t B, int32_t V, int32_t H, int32_t W, int32_t recompute);
+/* includes the qkv bias gradient's partial rows at the larger of the two producers' counts: the column-sum kernel's
+ * (B * lpad / 128) and the attention backward's (B * dgs_dit_attention_backward_slots(L): more when L % 256 > L / 256 + 2) */
 size_t dgs_dit_backward_workspace_bytes(const DgsDitModel* m, int32_t B, int32_t V, int32_t H, int32_t W);
-/* same outputs as dgs_dit_forward (a->workspace is not used); B <= 4 */
+/* same outputs as dgs_dit_forward (a->workspace is not used).  Both training calls: B <= 4 and B * n_gaussians <= 8 (the rows of
+ * the upsampler head's backward), anything else is DGS_ERR_INVALID_ARGUMENT before a kernel is enqueued */
 int dgs_dit_forward_train(const DgsDitModel* m, const DgsDitForwardArgs* a, void* saved, size_t saved_bytes, dgs_stream_t stream);
 int dgs_dit_backward(const DgsDitModel* m, const DgsDitModelT* mt, const DgsDitGrads* grads, const DgsDitBackwardArgs* a,
                      dgs_stream_t stream);

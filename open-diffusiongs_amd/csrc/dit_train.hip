@@ -88,9 +88,11 @@ struct BwdScratch {
     // slabs of per-workgroup partial column sums (dit_backward_elementwise.hip; summed by col_reduce in slot order)
     float* ln_part[2];       // [M / 32][3W]   LayerNorm backward: shift | scale | weight     ([0]: LN2 / heads / input LN, [1]: LN1)
     float* gate_part[2];     // [M / 64][2W]   gate_mul: gate gradient | bias gradient         ([0]: MLP branch, [1]: attention branch)
-    float *fc1b_part, *qkvb_part;   // [M / 128][4W], [M / 128][3W]   bias gradients of fc1 / qkv
+    float *fc1b_part, *qkvb_part;   // [M / 128][4W], [qkvb_rows][3W]   bias gradients of fc1 / qkv
+    size_t qkvb_rows;        // max(M / 128 (column-sum kernel), B * dgs_dit_attention_backward_slots(L) (attention backward's by-product:
+                             // one row per 256-token block AND per single tail token, more than M / 128 when L % 256 > L / 256 + 2))
     float* rl_part;          // [nmod / 256][B * W]   dx of the adaLN Linear
-    static BwdScratch carve(void* buf, const DgsDitModel* m, size_t B, size_t lpad, size_t* bytes) {
+    static BwdScratch carve(void* buf, const DgsDitModel* m, size_t B, size_t lpad, int L, size_t* bytes) {
         Carver c(buf);
         BwdScratch s;
         const size_t M = B * lpad, W = (size_t)m->width, pp = (size_t)m->patch * m->patch;
@@ -113,7 +115,10 @@ struct BwdScratch {
         s.xre = c.take<float>(M * W);
         const size_t ln_blk = M / ln_backward_rows_per_block((int)lpad, (int)M, ln_backward_compute_units());
         for (int i = 0; i < 2; ++i) { s.ln_part[i] = c.take<float>(ln_blk * 3 * W); s.gate_part[i] = c.take<float>(M / 64 * 2 * W); }
-        s.fc1b_part = c.take<float>((M + 127) / 128 * 4 * W); s.qkvb_part = c.take<float>((M + 127) / 128 * 3 * W);
+        s.fc1b_part = c.take<float>((M + 127) / 128 * 4 * W);
+        const size_t colsum_rows = (M + 127) / 128, attn_rows = B * (size_t)dgs_dit_attention_backward_slots(L);
+        s.qkvb_rows = attn_rows > colsum_rows ? attn_rows : colsum_rows;
+        s.qkvb_part = c.take<float>(s.qkvb_rows * 3 * W);
         const size_t nmod_rows = (6 * (size_t)m->layers + 4) * W;
         s.rl_part = c.take<float>((nmod_rows + ROWLINEAR_BWD_ROWS - 1) / ROWLINEAR_BWD_ROWS * B * W);
         if (bytes) *bytes = c.bytes();
@@ -196,14 +201,15 @@ int block_forward_train(const DgsDitModel* m, int i, const BlockSaved& k, float*
 extern "C" size_t dgs_dit_backward_workspace_bytes(const DgsDitModel* m, int32_t B, int32_t V, int32_t H, int32_t W) {
     if (!m || B <= 0) return 0;
     size_t b = 0;
-    BwdScratch::carve(nullptr, m, (size_t)B, (size_t)dgs_dit_lpad(tokens_of(m, V, H, W)), &b);
+    BwdScratch::carve(nullptr, m, (size_t)B, (size_t)dgs_dit_lpad(tokens_of(m, V, H, W)), tokens_of(m, V, H, W), &b);
     return b;
 }
 
 // Training-mode forward: same kernels as dgs_dit_forward, but q|k|v stay in one tensor (+ its transposed copy), the
 // residual stream is written out of place, and every tensor the backward needs lands in the `saved` arena.
 extern "C" int dgs_dit_forward_train(const DgsDitModel* m, const DgsDitForwardArgs* a, void* saved, size_t saved_bytes, dgs_stream_t stream) {
-    if (!m || !a || !saved || a->B <= 0 || a->B > 4 || m->layers > 64) return DGS_ERR_INVALID_ARGUMENT;   // B * n_gaussians <= 8 rows
+    if (!m || !a || !saved || a->B <= 0 || a->B > 4 || m->layers > 64) return DGS_ERR_INVALID_ARGUMENT;
+    if (a->B * m->n_gaussians > 8) return DGS_ERR_INVALID_ARGUMENT;   // the upsampler head's backward takes <= 8 rows
     if (m->width % 256 || m->width != m->heads * 64 || a->H % m->patch || a->W % m->patch || m->gs_channels != 14 || m->in_channels != 9)
         return DGS_ERR_INVALID_ARGUMENT;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -299,6 +305,7 @@ extern "C" int dgs_dit_backward(const DgsDitModel* m, const DgsDitModelT* mt, co
                                 dgs_stream_t stream) {
     if (!m || !mt || !gr || !a || a->B <= 0 || a->B > 4 || !a->saved || !a->workspace) return DGS_ERR_INVALID_ARGUMENT;
     if (!a->dxyz || !a->dfeatures || !a->dscaling || !a->drotation || !a->dopacity || !a->ray_d) return DGS_ERR_INVALID_ARGUMENT;
+    if (a->B * m->n_gaussians > 8) return DGS_ERR_INVALID_ARGUMENT;   // rows of the upsampler head's backward
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int B = a->B, V = a->V, H = a->H, Wd = a->W, W = m->width, ng = m->n_gaussians, C = m->gs_channels;
     const int L = tokens_of(m, V, H, Wd), lpad = dgs_dit_lpad(L), M = B * lpad;
@@ -307,8 +314,10 @@ extern "C" int dgs_dit_backward(const DgsDitModel* m, const DgsDitModelT* mt, co
     size_t need = 0;
     DitSaved sv = DitSaved::carve(a->saved, m, (size_t)B, (size_t)lpad, L, a->recompute, &need);
     if (a->saved_bytes < need) return DGS_ERR_ALLOC;
-    BwdScratch ws = BwdScratch::carve(a->workspace, m, (size_t)B, (size_t)lpad, &need);
+    BwdScratch ws = BwdScratch::carve(a->workspace, m, (size_t)B, (size_t)lpad, L, &need);
     if (a->workspace_bytes < need) return DGS_ERR_ALLOC;
+    // rows the attention backward writes into qkvb_part (its tail rule lives in dit_attention_backward.hip) against the rows carved
+    if ((size_t)B * (size_t)dgs_dit_attention_backward_slots(L) > ws.qkvb_rows) return DGS_ERR_INVALID_ARGUMENT;
 
     // No accumulator is filled with atomics: every column sum goes through a slab of per-workgroup partial rows and col_reduce
     // (dit_backward_elementwise.hip), so two passes over the same inputs give the same bits.  What is zeroed here: the decoder
@@ -351,7 +360,7 @@ extern "C" int dgs_dit_backward(const DgsDitModel* m, const DgsDitModelT* mt, co
     // ---- upsampler head (the learned-token rows) ----
     RowLinBwdParams ub{};
     ub.M = B * ng; ub.N = C; ub.K = W; ub.x = sv.upn; ub.W = m->up_w; ub.dy = ws.dup; ub.dW = gr->up_w; ub.dx = ws.dupn;
-    if (ub.M > 8) return DGS_ERR_INVALID_ARGUMENT;
+    if (ub.M > 8) return DGS_ERR_INVALID_ARGUMENT;      // cannot fire: rejected before the first launch
     DGS_TRY(launch_rowlinear_backward(ub, st));
     for (int b = 0; b < B; ++b) {
         LnBwdParams lu{};

@@ -86,3 +86,70 @@ def gradient_errors(grads, ref):
             rec["worst_row"] = float(d.norm(dim=1).max() / r.norm(dim=1).max().clamp_min(1e-30))
         out[k] = rec
     return out
+
+
+# ---- whole-model cases at other learned-token (n_gaussians) and view counts ----------------------------------------------------
+# (n_gaussians, B, V, res, layers, scene) at patch 8.  L = n_gaussians + V (res / 8)^2:
+#   264, 520: eight tail tokens behind one / two 256-token blocks (MFMA tail items in the GEMMs, one attention-backward workgroup per
+#             tail token: 9 / 10 partial rows of the qkv bias gradient against 4 / 6 that lpad / 128 gives);
+#   260 x 2 samples, 257 x 3, 259 (scene): tails of 4, 1 (one-row GEMV) and 3 tokens;  322, 194: no learned-token tail rule applies
+#   (five and three views: the generic ragged last tile).
+# The one-layer cases stay at one layer: the slab carved behind the qkv bias partials (the adaLN Linear's, sized by the layer count) is
+# then smaller than the rows a too-small carve would miss, so those rows leave the workspace instead of landing in a slab that is
+# rewritten before it is read.
+LEARNED_TOKEN_CASES = [(8, 1, 4, 64, 1, False), (8, 1, 2, 128, 1, False), (4, 2, 4, 64, 1, False), (1, 3, 4, 64, 2, False),
+                       (3, 1, 4, 64, 2, True), (2, 1, 5, 64, 2, False), (2, 1, 3, 64, 2, False)]
+# (n_gaussians, V) of the forward-only cases at res 64, one sample: L = 257, 259, 264, 268 (outside every tail rule), 194
+LEARNED_TOKEN_FORWARD_CASES = [(1, 4), (3, 4), (8, 4), (12, 4), (2, 3)]
+
+GUARD_BYTE, GUARD_BYTES = 0xA5, 1 << 16
+
+
+def learned_token_cfg(ng, layers, scene, width):
+    return D.Cfg(width=width, num_layers=layers, n_gaussians=ng, scene=scene, ray_pe_type="plk" if scene else "relative_plk",
+                 range_far=50.0)
+
+
+def learned_token_engine(cfg, sd, device, lib=None):
+    from dgs_amd.dit import DitEngine
+    return DitEngine(sd, width=cfg.width, num_layers=cfg.num_layers, n_gaussians=cfg.n_gaussians, ray_pe_type=cfg.ray_pe_type,
+                     scene=cfg.scene, range_near=cfg.range_near, range_far=cfg.range_far, device=device, lib=lib)
+
+
+def guard_arena(eng, ar, which):
+    """Swap the arena's `which` ('bws': backward workspace, 'saved': activation arena) for a view of a larger buffer of the same device
+    and dtype whose tail (64 KiB behind the view) is filled with 0xA5.  The view keeps the contents and numel() -- the byte counts the
+    engine hands to the library do not change -- so a kernel that writes past the size the library itself asked for lands in memory
+    this test owns.  Returns a checker that asserts the tail is untouched (and synchronises first on a GPU)."""
+    old = ar[which]
+    n = old.numel()
+    big = torch.empty(n + GUARD_BYTES, dtype=old.dtype, device=old.device)
+    big[:n].copy_(old)
+    big[n:].fill_(GUARD_BYTE)
+    ar[which] = big[:n]
+    tr = eng._train
+    if tr.get("current") is ar:      # the engine's mirrors of the most recently used arena
+        tr[which] = ar[which]
+
+    def check():
+        if big.device.type == "cuda":
+            torch.cuda.synchronize(big.device)
+        dirty = int((big[n:] != GUARD_BYTE).sum())
+        assert dirty == 0, f"{dirty} bytes written past the end of the {n}-byte '{which}' arena"
+    return check
+
+
+def guarded_forward_train(eng, images, ray_o, ray_d, t, recompute=False):
+    """eng.forward_train with both arenas of the pass under guard_arena.  Returns (outputs, aligned, arena, check): pass the arena to
+    eng.backward(..., arena=arena), then call check() -- it is also run on the activation arena right after the forward."""
+    B, V, _, H, W = images.shape
+    ar = eng._arena(B, V, H, W, bool(recompute), False)
+    checks = [guard_arena(eng, ar, "saved"), guard_arena(eng, ar, "bws")]
+    out, aligned = eng.forward_train(images, ray_o, ray_d, t, recompute=recompute)
+    assert eng._train["current"] is ar
+    checks[0]()
+
+    def check():
+        for c in checks:
+            c()
+    return out, aligned, ar, check

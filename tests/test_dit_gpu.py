@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from dgs_amd import _native
-from dit_util import golden_case, rel_l2, synth_inputs
+from dit_util import LEARNED_TOKEN_FORWARD_CASES, golden_case, rel_l2, synth_inputs
 from oracle import dit_oracle as D
 
 pytestmark = pytest.mark.gpu
@@ -303,6 +303,41 @@ def test_full_model_256_vs_fp32_oracle_on_gpu():
 def test_full_model_512_vs_fp32_oracle_on_gpu():
     """BASELINE configs[4] (scene model, 512^2): L = 16,386 tokens, P = 1,048,578 Gaussians, all 24 blocks."""
     _full_model_case(512, 1, DEV, scene=True)
+
+
+@pytest.mark.parametrize("ng,V", LEARNED_TOKEN_FORWARD_CASES)
+def test_forward_at_other_learned_token_and_view_counts(ng, V):
+    """The inference forward at width 1024 (the shipped GEMM dispatch: GEMV rows need K >= 512), two blocks, at token counts other
+    than 256 k + 2: one learned token (one-row GEMV), 3 and 8 (MFMA tail items, the LayerNorm+GEMM pair as two launches), 12 (L = 268,
+    outside every tail rule) and three views (L = 194).  _full_model_case's bars; the learned tokens' own rows also on their own."""
+    import os
+    from dit_util import learned_token_cfg, learned_token_engine
+    cfg = learned_token_cfg(ng, 2, False, width=1024)
+    sd = D.parity_state_dict(cfg, seed=11)
+    B, res = 1, 64
+    images, ray_o, ray_d, t, _, _ = synth_inputs(cfg, B, V, res, seed=3)
+    eng = learned_token_engine(cfg, sd, DEV)
+    out, aligned = eng.image_to_gaussians(images, ray_o, ray_d, t, return_tokens=True)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        ref, ref_aligned = D.image_to_gaussians({k: v.to(DEV) for k, v in sd.items()}, cfg, images.to(DEV), ray_o.to(DEV), ray_d.to(DEV),
+                                                t.to(DEV), return_tokens=True)
+    cat = lambda o: torch.cat([o[k][:, :ng].reshape(B, ng, -1) for k in FIELDS], -1)
+    errs = {"tokens": rel_l2(out["tokens"], ref["tokens"]), "learned_token_rows": rel_l2(out["tokens"][:, :ng], ref["tokens"][:, :ng]),
+            "learned_token_gaussians": rel_l2(cat(out), cat(ref)), "aligned": rel_l2(aligned, ref_aligned)}
+    errs.update({k: rel_l2(out[k], ref[k]) for k in FIELDS})
+    line = f"forward n_gaussians={ng} V={V} res={res} L={eng.num_tokens(V, res, res)}: " + " ".join(f"{k}={e:.2e}" for k, e in errs.items())
+    print(line)
+    if os.environ.get("DGS_LEARNED_TOKEN_PARITY_DUMP"):
+        with open(os.environ["DGS_LEARNED_TOKEN_PARITY_DUMP"], "a") as f:
+            f.write(line + "\n")
+    assert out["tokens"].shape == ref["tokens"].shape
+    assert errs["tokens"] < 1e-2 and errs["learned_token_rows"] < 1e-2, errs
+    for k in FIELDS:
+        assert out[k].shape == ref[k].shape, k
+        assert errs[k] < 2e-2, (k, errs)
+    assert errs["learned_token_gaussians"] < 2e-2 and errs["aligned"] < 2e-2, errs
+    assert all(torch.isfinite(out[k]).all() for k in FIELDS)
 
 
 def test_denoiser_forward_end_to_end_256():
