@@ -5,12 +5,19 @@
 // once so that the transposed rows leave as 16-byte stores too).  256 threads, 16 bytes per lane and access, no atomics, nothing
 // depends on the order of the tiles.
 #include "dgs_device.h"
+#include "dgs_ema.h"
 #include "dgs_optim.h"
 #include "dit_common.h"
+#include "ema_arith.h"
 
 namespace dgs {
 
 struct AdamWHyper { float decay, one_minus_b1, b2, one_minus_b2, inv_bc2_sqrt, eps, step_size; const float* grad_sumsq; float max_grad_norm; };
+// kEma = true: the launch also keeps the EMA shadows (include/dgs_ema.h).  A tensor's shadow sits where its first moment sits, in a
+// buffer of the same layout: ema_base + (t.m - m_base).  kEma = false takes AdamWHyper itself: the kernel dgs_adamw_step always had.
+struct AdamWEmaHyper : AdamWHyper { float* ema_base; const float* m_base; float one_minus_decay; };
+template <bool kEma> struct HyperOf { typedef AdamWHyper type; };
+template <> struct HyperOf<true> { typedef AdamWEmaHyper type; };
 
 // ---- gradient norm for the global-norm clip (Lightning `gradient_clip_val`, torch.nn.utils.clip_grad_norm_) ----
 // One partial per kSumsqChunk consecutive elements, WRITTEN (not accumulated) by the workgroup that owns the chunk: lanes sum their
@@ -74,6 +81,8 @@ __device__ __forceinline__ float clip_coef(const AdamWHyper& h) {
     return c < 1.0f ? c : 1.0f;
 }
 
+// NOTE: this function has a twin, adamw_one_spelled below, that the EMA form of the kernel uses and that must produce the same bits:
+// change the arithmetic here and the twin has to follow (tests/test_ema.py's GPU tests compare the two kernels bit for bit).
 __device__ __forceinline__ float adamw_one(float& p, float g, float& m, float& v, const AdamWHyper& h) {
     p = p * h.decay;
     m = m + (g - m) * h.one_minus_b1;
@@ -83,7 +92,44 @@ __device__ __forceinline__ float adamw_one(float& p, float g, float& m, float& v
     return p;
 }
 
-__global__ __launch_bounds__(256) void adamw_refresh_kernel(const DgsAdamWTensor* __restrict__ tab, int n_tensors, AdamWHyper h) {
+__device__ __forceinline__ void ema_four(float4& e, const float4& p, float omd) {
+    e.x = ema_one(e.x, p.x, omd); e.y = ema_one(e.y, p.y, omd); e.z = ema_one(e.z, p.z, omd); e.w = ema_one(e.w, p.w, omd);
+}
+
+// EMA on or off must not move training by a bit, and adamw_one leaves the choice of which multiply fuses with which add to the compiler
+// (optim.hip is built with the default contraction mode; changing that would move AdamW's own bits).  With the EMA's operations among
+// them the compiler chose differently -- in the scalar tail it packed p * decay and step_size * (m / denom) into one two-wide multiply
+// and subtracted, where dgs_adamw_step's kernel has one FMA -- and parameters differed in the last bit.  So the kEma form spells out the
+// operations dgs_adamw_step's kernel consists of (five FMAs, four multiplies, a correctly rounded sqrt and divide), with contraction off
+// so that nothing else can fuse.  That kernel's own paths differ in one place: in v = v * b2 + ((1 - b2) * g) * g the float4 paths
+// (kPacked) fuse the second product into the add, the scalar tail the first.  tests/test_ema.py compares the two kernels bit for bit
+// on the GPU, on every path.
+template <bool kPacked>
+__device__ __forceinline__ void adamw_one_spelled(float& p, float g, float gc, float& m, float& v, const AdamWHyper& h) {
+#pragma clang fp contract(off)
+    const float gs = g * gc;
+    const float gm = __builtin_fmaf(g, gc, -m);                        // g * gc - m
+    m = __builtin_fmaf(gm, h.one_minus_b1, m);
+    const float t = h.one_minus_b2 * gs;
+    if constexpr (kPacked) v = __builtin_fmaf(gs, t, v * h.b2);
+    else v = __builtin_fmaf(v, h.b2, t * gs);
+    const float denom = __builtin_fmaf(sqrtf(v), h.inv_bc2_sqrt, h.eps);
+    const float s = h.step_size * (m / denom);
+    p = __builtin_fmaf(p, h.decay, -s);
+}
+
+template <bool kEma, bool kPacked>
+__device__ __forceinline__ void adamw_step_one(float& p, float g, float gc, float& m, float& v, const AdamWHyper& h) {
+#ifdef HIPEMU
+    adamw_one(p, g * gc, m, v, h);                                     // the emulator build never contracts: one form for both
+#else
+    if constexpr (kEma) adamw_one_spelled<kPacked>(p, g, gc, m, v, h);
+    else adamw_one(p, g * gc, m, v, h);
+#endif
+}
+
+template <bool kEma>
+__global__ __launch_bounds__(256) void adamw_refresh_kernel(const DgsAdamWTensor* __restrict__ tab, int n_tensors, typename HyperOf<kEma>::type h) {
     __shared__ __attribute__((aligned(16))) unsigned short tile[64][64 + 8];     // bf16 block for the transposed copy (rows padded: 144 B)
     const int tid = threadIdx.x, bid = blockIdx.x;
     // the tensor this tile belongs to: the last entry whose first_tile <= bid (uniform: scalar loads)
@@ -99,6 +145,9 @@ __global__ __launch_bounds__(256) void adamw_refresh_kernel(const DgsAdamWTensor
     // 16-mixed training does with such a step (torch.cuda.amp.GradScaler.step skips the optimizer when it found inf / NaN).
     if (h.grad_sumsq != nullptr && (__float_as_uint(h.grad_sumsq[0]) & 0x7f800000u) == 0x7f800000u) return;   // exponent all ones: inf / NaN
     const float gc = clip_coef(h);                                 // 1 without a clip: g * 1.0f is g
+    float* shadow = nullptr;                                       // the EMA of the NEW value rides along: 4 B read + 4 B written per parameter
+    float omd = 0.0f;
+    if constexpr (kEma) { shadow = h.ema_base + (t.m - h.m_base); omd = h.one_minus_decay; }
     if (t.copy_t == nullptr) {
         // ---- flat tile: elements [local * 4096, +4096) ----
         const long long n = t.rows * t.cols, base = (long long)local * 4096;
@@ -111,19 +160,23 @@ __global__ __launch_bounds__(256) void adamw_refresh_kernel(const DgsAdamWTensor
                 float4 p = *reinterpret_cast<const float4*>(t.p + i);
                 const float4 g = *reinterpret_cast<const float4*>(t.g + i);
                 float4 m = *reinterpret_cast<const float4*>(t.m + i), v = *reinterpret_cast<const float4*>(t.v + i);
-                adamw_one(p.x, g.x * gc, m.x, v.x, h); adamw_one(p.y, g.y * gc, m.y, v.y, h);
-                adamw_one(p.z, g.z * gc, m.z, v.z, h); adamw_one(p.w, g.w * gc, m.w, v.w, h);
+                float4 e;
+                if constexpr (kEma) e = *reinterpret_cast<const float4*>(shadow + i);
+                adamw_step_one<kEma, true>(p.x, g.x, gc, m.x, v.x, h); adamw_step_one<kEma, true>(p.y, g.y, gc, m.y, v.y, h);
+                adamw_step_one<kEma, true>(p.z, g.z, gc, m.z, v.z, h); adamw_step_one<kEma, true>(p.w, g.w, gc, m.w, v.w, h);
                 *reinterpret_cast<float4*>(t.p + i) = p;
                 *reinterpret_cast<float4*>(t.m + i) = m;
                 *reinterpret_cast<float4*>(t.v + i) = v;
+                if constexpr (kEma) { ema_four(e, p, omd); *reinterpret_cast<float4*>(shadow + i) = e; }
                 if (t.copy_kind == DGS_OPTIM_COPY_BF16)
                     *reinterpret_cast<uint2*>(static_cast<bf16_t*>(t.copy) + i) = make_uint2(pack_bf2(p.x, p.y), pack_bf2(p.z, p.w));
                 else if (t.copy_kind == DGS_OPTIM_COPY_F32) *reinterpret_cast<float4*>(static_cast<float*>(t.copy) + i) = p;
             } else {
                 for (int e = 0; e < 4 && i + e < n; ++e) {
                     float p = t.p[i + e], m = t.m[i + e], v = t.v[i + e];
-                    adamw_one(p, t.g[i + e] * gc, m, v, h);
+                    adamw_step_one<kEma, false>(p, t.g[i + e], gc, m, v, h);
                     t.p[i + e] = p; t.m[i + e] = m; t.v[i + e] = v;
+                    if constexpr (kEma) shadow[i + e] = ema_one(shadow[i + e], p, omd);
                     if (t.copy_kind == DGS_OPTIM_COPY_BF16) static_cast<bf16_t*>(t.copy)[i + e] = (bf16_t)(pack_bf2(p, 0.0f) & 0xffffu);
                     else if (t.copy_kind == DGS_OPTIM_COPY_F32) static_cast<float*>(t.copy)[i + e] = p;
                 }
@@ -142,11 +195,14 @@ __global__ __launch_bounds__(256) void adamw_refresh_kernel(const DgsAdamWTensor
         float4 p = *reinterpret_cast<const float4*>(t.p + i);
         const float4 g = *reinterpret_cast<const float4*>(t.g + i);
         float4 m = *reinterpret_cast<const float4*>(t.m + i), v = *reinterpret_cast<const float4*>(t.v + i);
-        adamw_one(p.x, g.x * gc, m.x, v.x, h); adamw_one(p.y, g.y * gc, m.y, v.y, h);
-        adamw_one(p.z, g.z * gc, m.z, v.z, h); adamw_one(p.w, g.w * gc, m.w, v.w, h);
+        float4 e;
+        if constexpr (kEma) e = *reinterpret_cast<const float4*>(shadow + i);
+        adamw_step_one<kEma, true>(p.x, g.x, gc, m.x, v.x, h); adamw_step_one<kEma, true>(p.y, g.y, gc, m.y, v.y, h);
+        adamw_step_one<kEma, true>(p.z, g.z, gc, m.z, v.z, h); adamw_step_one<kEma, true>(p.w, g.w, gc, m.w, v.w, h);
         *reinterpret_cast<float4*>(t.p + i) = p;
         *reinterpret_cast<float4*>(t.m + i) = m;
         *reinterpret_cast<float4*>(t.v + i) = v;
+        if constexpr (kEma) { ema_four(e, p, omd); *reinterpret_cast<float4*>(shadow + i) = e; }
         const uint2 b = make_uint2(pack_bf2(p.x, p.y), pack_bf2(p.z, p.w));
         if (t.copy_kind == DGS_OPTIM_COPY_BF16) *reinterpret_cast<uint2*>(static_cast<bf16_t*>(t.copy) + i) = b;
         else if (t.copy_kind == DGS_OPTIM_COPY_F32) *reinterpret_cast<float4*>(static_cast<float*>(t.copy) + i) = p;
@@ -190,10 +246,10 @@ extern "C" int32_t dgs_adamw_plan(DgsAdamWTensor* tab, int32_t n) {
     return (int32_t)tiles;
 }
 
-extern "C" int dgs_adamw_step(const DgsAdamWArgs* a, dgs_stream_t stream) {
+// the launch's constants from the caller's arguments; false: arguments dgs_adamw_step refuses
+static bool adamw_hyper(const DgsAdamWArgs* a, dgs::AdamWHyper& h) {
     if (!a || !a->tensors || a->n_tensors <= 0 || a->n_tiles <= 0 || !(a->bias_correction1 > 0.0f) || !(a->bias_correction2_sqrt > 0.0f))
-        return DGS_ERR_INVALID_ARGUMENT;
-    dgs::AdamWHyper h;
+        return false;
     h.decay = 1.0f - a->lr * a->weight_decay;
     h.one_minus_b1 = 1.0f - a->beta1;
     h.b2 = a->beta2;
@@ -203,8 +259,26 @@ extern "C" int dgs_adamw_step(const DgsAdamWArgs* a, dgs_stream_t stream) {
     h.step_size = a->lr / a->bias_correction1;
     h.grad_sumsq = a->max_grad_norm > 0.0f ? a->grad_sumsq : nullptr;
     h.max_grad_norm = a->max_grad_norm;
-    if (a->max_grad_norm > 0.0f && !a->grad_sumsq) return DGS_ERR_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(dgs::adamw_refresh_kernel, dim3(a->n_tiles), dim3(256), 0, static_cast<hipStream_t>(stream), a->tensors, a->n_tensors, h);
+    return !(a->max_grad_norm > 0.0f && !a->grad_sumsq);
+}
+
+extern "C" int dgs_adamw_step(const DgsAdamWArgs* a, dgs_stream_t stream) {
+    dgs::AdamWHyper h;
+    if (!adamw_hyper(a, h)) return DGS_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(dgs::adamw_refresh_kernel<false>, dim3(a->n_tiles), dim3(256), 0, static_cast<hipStream_t>(stream), a->tensors, a->n_tensors, h);
+    return hipGetLastError() == hipSuccess ? DGS_OK : DGS_ERR_DEVICE;
+}
+
+extern "C" int dgs_adamw_ema_step(const DgsAdamWArgs* a, const DgsEmaFusedArgs* ema, dgs_stream_t stream) {
+    dgs::AdamWEmaHyper h;
+    if (!ema || !ema->ema_base || !ema->m_base || !adamw_hyper(a, h)) return DGS_ERR_INVALID_ARGUMENT;
+    // every t.m is 16-byte aligned (dgs_adamw_plan): with both bases aligned so is every shadow
+    if ((reinterpret_cast<uintptr_t>(ema->ema_base) & 15) || (reinterpret_cast<uintptr_t>(ema->m_base) & 15)) return DGS_ERR_INVALID_ARGUMENT;
+    if (!(ema->one_minus_decay >= 0.0f && ema->one_minus_decay <= 1.0f)) return DGS_ERR_INVALID_ARGUMENT;
+    h.ema_base = ema->ema_base;
+    h.m_base = ema->m_base;
+    h.one_minus_decay = ema->one_minus_decay;
+    hipLaunchKernelGGL(dgs::adamw_refresh_kernel<true>, dim3(a->n_tiles), dim3(256), 0, static_cast<hipStream_t>(stream), a->tensors, a->n_tensors, h);
     return hipGetLastError() == hipSuccess ? DGS_OK : DGS_ERR_DEVICE;
 }
 

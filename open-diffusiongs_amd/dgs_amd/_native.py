@@ -449,8 +449,37 @@ def _declare_field(L):
     return L
 
 
+class DgsEmaFusedArgs(ctypes.Structure):
+    _fields_ = [("ema_base", ctypes.c_void_p), ("m_base", ctypes.c_void_p), ("one_minus_decay", ctypes.c_float)]
+
+
+class DgsEmaTensor(ctypes.Structure):
+    _fields_ = [("p", ctypes.c_void_p), ("ema", ctypes.c_void_p), ("copy", ctypes.c_void_p), ("copy_t", ctypes.c_void_p),
+                ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("copy_kind", ctypes.c_int32), ("first_tile", ctypes.c_int32)]
+
+
+class DgsEmaArgs(ctypes.Structure):
+    _fields_ = [("tensors", ctypes.c_void_p), ("n_tensors", ctypes.c_int32), ("n_tiles", ctypes.c_int32),
+                ("one_minus_decay", ctypes.c_float), ("update", ctypes.c_int32), ("copy_source", ctypes.c_int32)]
+
+
+EMA_SOURCE_NONE, EMA_SOURCE_P, EMA_SOURCE_EMA = 0, 1, 2
+# every symbol include/dgs_ema.h declares (checked by tests/test_ema.py)
+EMA_SYMBOLS = ["dgs_adamw_ema_step", "dgs_ema_plan", "dgs_ema_apply"]
+
+
+def _declare_ema(L):
+    L.dgs_adamw_ema_step.restype = ctypes.c_int
+    L.dgs_adamw_ema_step.argtypes = [ctypes.POINTER(DgsAdamWArgs), ctypes.POINTER(DgsEmaFusedArgs), ctypes.c_void_p]
+    L.dgs_ema_plan.restype = ctypes.c_int32
+    L.dgs_ema_plan.argtypes = [ctypes.POINTER(DgsEmaTensor), ctypes.c_int32]
+    L.dgs_ema_apply.restype = ctypes.c_int
+    L.dgs_ema_apply.argtypes = [ctypes.POINTER(DgsEmaArgs), ctypes.c_void_p]
+    return L
+
+
 _declare_raster = _declare
 
 
-def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field prototypes on one library)
-    return _declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L))))))
+def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA prototypes on one library)
+    return _declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L)))))))

@@ -383,7 +383,8 @@ class DGSDenoiser(nn.Module):
         """The device-resident bf16 copy of the parameters + workspaces.  Built once; when parameter versions change
         (optimizer.step(), load_state_dict) the new values are copied INTO the existing buffers (no reallocation of the
         weights, the activation arenas or the flat gradient buffer).  Updates that bypass version counters (`p.data = ...`,
-        an EMA swap) need an explicit `refresh_engine_weights()`."""
+        a callback that swaps EMA weights into the parameters) need an explicit `refresh_engine_weights()`; `dgs_amd.ema.EMA.swapped`
+        does not touch the parameters at all: it rewrites the copies themselves."""
         version = tuple(p._version for p in self.parameters())
         if self._engine is None:
             c = self.cfg
@@ -393,11 +394,18 @@ class DGSDenoiser(nn.Module):
                                      range_near=c.range_setting_near, range_far=c.range_setting_far, device=self.device,
                                      lib=self._lib)
         elif version != self._engine_version:
+            self._refuse_refresh_while_swapped()
             self._engine.refresh_weights(self.state_dict())
         self._engine_version = version
         return self._engine
 
+    def _refuse_refresh_while_swapped(self):
+        if getattr(self, "_ema_swapped", False):
+            raise RuntimeError("DGSDenoiser: the parameters changed (or a refresh was asked for) inside `ema.swapped(model)`: the engine's "
+                               "copies hold the averaged weights there, and refreshing them would silently end that; leave the block first")
+
     def refresh_engine_weights(self):
+        self._refuse_refresh_while_swapped()
         if self._engine is not None:
             self._engine.refresh_weights(self.state_dict())
             self._engine_version = tuple(p._version for p in self.parameters())

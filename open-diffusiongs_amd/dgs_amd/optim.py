@@ -19,6 +19,17 @@ from . import _native
 from .dit import _stream
 
 
+def flat_offsets(numels):
+    """Element offsets of tensors of `numels` elements in one flat fp32 buffer, every slice 256-byte aligned (64 elements), and the
+    buffer's length: the layout of FusedAdamW's moments -- and of the EMA shadows (dgs_amd/ema.py), which the fused launch finds at the
+    first moment's offset."""
+    offsets, o = [], 0
+    for n in numels:
+        offsets.append(o)
+        o += (int(n) + 63) // 64 * 64
+    return offsets, o
+
+
 class FusedAdamW(torch.optim.Optimizer):
     refreshes_engine = True          # DataParallelTrainer: the engine's weight copies are written by step() itself
 
@@ -30,14 +41,23 @@ class FusedAdamW(torch.optim.Optimizer):
         self.step_count = 0
         self._named = [(n, p) for n, p in model.named_parameters()]
         dev = self._named[0][1].device
-        sizes = [(p.numel() + 63) // 64 * 64 for _, p in self._named]          # 256-byte aligned slices
-        self.exp_avg = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
+        self._offsets, total = flat_offsets(p.numel() for _, p in self._named)          # 256-byte aligned slices
+        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros_like(self.exp_avg)
-        self._offsets, o = [], 0
-        for s in sizes:
-            self._offsets.append(o)
-            o += s
         self._table = None          # (device table, n_tensors, n_tiles, the pointers it was built from)
+        self._table_names = ()      # the parameters in it (those that have a gradient)
+        self._ema = None            # attach_ema: the shadows are kept by the update launch
+
+    def attach_ema(self, ema):
+        """The EMA of the weights (dgs_amd.ema.EMA) rides in the update launch from now on: on the steps `ema.should_apply(step_count)`
+        selects, step() calls dgs_adamw_ema_step instead of dgs_adamw_step.  None detaches."""
+        if ema is not None:
+            names = [n for n, _ in self._named]
+            if ema.param_names != names or ema.offsets != self._offsets or ema.flat.numel() != self.exp_avg.numel():
+                raise ValueError("FusedAdamW.attach_ema: the EMA was built for another model (parameter names / layout differ)")
+            if ema.flat.device != self.exp_avg.device or ema.flat.dtype != torch.float32:
+                raise ValueError("FusedAdamW.attach_ema: the shadows must be fp32 on the optimizer's device")
+        self._ema = ema
 
     # -- torch.optim.Optimizer surface the trainer / a scheduler touches ---------------------------------
     def zero_grad(self, set_to_none=True):
@@ -112,6 +132,7 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("FusedAdamW: dgs_adamw_plan rejected the tensor table")
         raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.exp_avg.device)
         self._table = (raw, len(entries), n_tiles, ptrs)
+        self._table_names = tuple(name for name, p in self._named if p.grad is not None)
         return self._table
 
     def step(self, closure=None, grad_sumsq=None, max_grad_norm=None):
@@ -136,14 +157,22 @@ class FusedAdamW(torch.optim.Optimizer):
         host, ev = probe
         ev.synchronize()
         if not math.isfinite(float(host[0])):
-            self.step_count -= 1
-            self.skipped_steps = getattr(self, "skipped_steps", 0) + 1
+            self._uncount_skipped()
+
+    def _uncount_skipped(self):
+        if self._ema is not None:
+            self._ema._step_was_skipped(self.step_count)       # the launch left the shadows alone: the schedule does not advance either
+        self.step_count -= 1
+        self.skipped_steps = getattr(self, "skipped_steps", 0) + 1
 
     def _step(self, grad_sumsq, max_grad_norm):
+        if getattr(self.model, "_ema_swapped", False):
+            raise RuntimeError("FusedAdamW.step inside `ema.swapped(model)`: the engine's copies hold the averaged weights")
         g = self.param_groups[0]
         raw, n, n_tiles, _ = self._plan()
         self._settle_previous()
         self.step_count += 1
+        ema = self._ema if self._ema is not None and self._ema.should_apply(self.step_count) else None
         b1, b2 = g["betas"]
         a = _native.DgsAdamWArgs()
         a.tensors, a.n_tensors, a.n_tiles = raw.data_ptr(), n, n_tiles
@@ -155,9 +184,16 @@ class FusedAdamW(torch.optim.Optimizer):
                 raise ValueError("FusedAdamW.step: max_grad_norm needs grad_sumsq (the device word holding the gradients' sum of squares)")
             self._keep_sumsq = grad_sumsq
             a.grad_sumsq, a.max_grad_norm = grad_sumsq.data_ptr(), float(max_grad_norm)
-        rc = self.lib.dgs_adamw_step(ctypes.byref(a), _stream(self.exp_avg.device))
+        if ema is None:
+            rc = self.lib.dgs_adamw_step(ctypes.byref(a), _stream(self.exp_avg.device))
+        else:
+            f = _native.DgsEmaFusedArgs()
+            f.ema_base, f.m_base, f.one_minus_decay = ema.flat.data_ptr(), self.exp_avg.data_ptr(), ema.one_minus_decay
+            rc = self.lib.dgs_adamw_ema_step(ctypes.byref(a), ctypes.byref(f), _stream(self.exp_avg.device))
         if rc != 0:
             raise RuntimeError(f"dgs_adamw_step: {_native.status_string(self.lib, rc)} (status {rc})")
+        if ema is not None:        # what the launch did not cover (parameters without a gradient, floating-point buffers), as torch ops
+            ema._applied_by_optimizer(self.step_count, self._table_names, grad_sumsq if a.grad_sumsq else None)
         if a.grad_sumsq and grad_sumsq.device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
             if getattr(self, "_skip_host", None) is None:
                 self._skip_host = torch.zeros(1, dtype=torch.float32).pin_memory()
@@ -166,7 +202,6 @@ class FusedAdamW(torch.optim.Optimizer):
             ev.record()
             self._skip_probe = (self._skip_host, ev)
         elif a.grad_sumsq and grad_sumsq.device.type != "cuda" and not math.isfinite(float(grad_sumsq.reshape(-1)[0])):
-            self.step_count -= 1                       # CPU emulation build: the word is at hand
-            self.skipped_steps = getattr(self, "skipped_steps", 0) + 1
+            self._uncount_skipped()                    # CPU emulation build: the word is at hand
         # the parameters were written through raw pointers: their version counters did not move, and the engine's copies are
         # already up to date -- DGSDenoiser.engine() must not refresh them again

@@ -17,6 +17,8 @@ gradient into ONE flat fp32 buffer in backward-completion order and calls back a
 the callback launches every bucket that just became final.  The parameters' .grad tensors ARE views of that buffer: the
 collective reduces them in place and nothing is copied in or out.  Averaging is folded into the loss scale.
 """
+import contextlib
+
 import torch
 
 from . import losses
@@ -29,7 +31,7 @@ class DataParallelTrainer:
     block) hands the model back: a later plain `loss.backward()` then returns gradients through autograd again."""
 
     def __init__(self, model, optimizer, bucket_bytes=None, accumulate_grad_batches=1, group=None, compress=None, force_collectives=False,
-                 max_grad_norm=None, broadcast_from=0, deterministic=None, lambda_ssim=None):
+                 max_grad_norm=None, broadcast_from=0, deterministic=None, lambda_ssim=None, ema=None):
         """deterministic (default on; DGS_RASTER_DETERMINISTIC=0 or False turns it off): the rasterizer backward without floating-point
         atomics (dgs_raster.h `scratch`), which makes the WHOLE step bit-reproducible -- the DiT backward, the bucketed all-reduce
         order, the norm and the AdamW launch already are -- for +0.10 of 1.07 ms of rasterizer backward at 4 views of 256^2
@@ -44,7 +46,12 @@ class DataParallelTrainer:
         broadcast_from: the rank whose parameters every rank starts from (DDP's init-time broadcast); None skips it.
         lambda_ssim: None (default) trains on the MSE term through losses.mse_psnr, as before.  A float -- 0.0 included: the reference
         evaluates and logs the term at weight 0 -- routes the step through losses.image_losses (loss = l2.mean() + lambda_ssim *
-        ssim_loss.mean(), one fused backward launch) and keeps the per-sample term in `last_ssim_loss`."""
+        ssim_loss.mean(), one fused backward launch) and keeps the per-sample term in `last_ssim_loss`.
+        ema: a dgs_amd.ema.EMA of this model (the reference's EMA callback, launch.py:205-228).  FusedAdamW keeps the shadows inside its
+        update launch; after any other optimizer's step -- when it was taken -- `ema.update(model)` is one more launch.  The EMA was
+        built before this trainer, i.e. before `broadcast_from` made the ranks' parameters equal: its shadows (cloned or loaded from
+        a checkpoint) are broadcast from the same rank here, once; after that no collective is needed, equal parameters and equal
+        shadows stay equal.  `with trainer.evaluate():` runs on the averaged weights."""
         self.model, self.opt = model, optimizer
         import os
         if deterministic is None:
@@ -89,6 +96,13 @@ class DataParallelTrainer:
         model._grads_in_place = True
         model._block_hook = self._on_gradients_final
         self._attach_grads()
+        self.ema = ema
+        if ema is not None and ema.model is not model:
+            raise ValueError("DataParallelTrainer: the EMA was built for another model")
+        if ema is not None and self.broadcast_bytes:
+            self.broadcast_bytes += ema.broadcast_shadows(src=broadcast_from, group=group)
+        if ema is not None and getattr(optimizer, "refreshes_engine", False):
+            optimizer.attach_ema(ema)
         self.lambda_ssim = None if lambda_ssim is None else float(lambda_ssim)
         self.last_psnr = None
         self.last_ssim_loss = None       # [b] of the last micro-batch when lambda_ssim is set
@@ -108,6 +122,11 @@ class DataParallelTrainer:
             elif self._raster_backend is not None and self._raster_was_deterministic is not None:
                 self._raster_backend.deterministic = self._raster_was_deterministic
                 self._raster_backend.deterministic_budget = self._raster_was_budget
+
+    def evaluate(self):
+        """Context manager: inside it the engine computes with the EMA weights (`ema.swapped(model)`: only its operand copies are
+        rewritten, and written back on the way out).  Without an EMA: nothing happens."""
+        return self.ema.swapped(self.model) if self.ema is not None else contextlib.nullcontext()
 
     def __enter__(self):
         return self
@@ -153,6 +172,8 @@ class DataParallelTrainer:
         m, K = self.model, self.accumulate
         if m._block_hook != self._on_gradients_final:
             raise RuntimeError("DataParallelTrainer.step after close() (or another trainer took the model over)")
+        if getattr(m, "_ema_swapped", False):
+            raise RuntimeError("DataParallelTrainer.step inside `evaluate()` / `ema.swapped(model)`: the engine holds the averaged weights")
         self._attach_grads()
         c2w = batch["c2w"] if render_c2w is None else render_c2w
         k = batch["fxfycxcy"] if render_fxfycxcy is None else render_fxfycxcy
@@ -193,6 +214,7 @@ class DataParallelTrainer:
                 else:
                     self._accum += self.fg.flat
         self.reducer.finish(average=False)
+        ema_after = self.ema if self.ema is not None and not getattr(self.opt, "refreshes_engine", False) else None
         if self.norm is not None:
             self.last_grad_sumsq = self.norm.total()
             if getattr(self.opt, "refreshes_engine", False):          # FusedAdamW: the scale rides in the update launch
@@ -205,8 +227,12 @@ class DataParallelTrainer:
                     coef = (self.max_grad_norm / (self.last_grad_sumsq.sqrt() + 1e-6)).clamp(max=1.0)
                     self.fg.flat.mul_(coef)
                     self.opt.step()
+                    if ema_after is not None:
+                        ema_after.update(m)
         else:
             self.opt.step()
+            if ema_after is not None:
+                ema_after.update(m)
         # weights changed: the engine's bf16 / transposed copies have to follow.  dgs_amd.optim.FusedAdamW writes them in the same launch
         # as the update; for any other optimizer they are refreshed EXPLICITLY -- DGSDenoiser.engine() only notices parameter version
         # counters, and an optimizer is free not to move them (foreach / fused implementations, `p.data` updates, EMA swaps)
