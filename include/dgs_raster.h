@@ -123,6 +123,16 @@ typedef struct DgsRasterForwardArgs {
                                     of the result bit-identical with the oracle.  Integer artefacts that do not depend on alpha
                                     (radii, tile lists, ranges, sort order) are identical in both; pass the same value to the
                                     backward.  */
+    /* ---- optional aux maps (appended: a zero-initialised tail is the colour-only call) ----
+     * Both or neither ([V,1,H,W] each, written for every pixel).  Over exactly the (pixel, Gaussian) pairs i that blend into the
+     * colour -- same skip rules, same 1/255 cut, same T < 1e-4 termination, same exact_exp mode --
+     *   out_alpha = sum_i alpha_i T_i = 1 - final_T
+     *   out_depth = sum_i alpha_i T_i z_i,   z_i = p_view.z of the Gaussian in that view
+     * i.e. UN-NORMALISED expected depth without a background term (divide by out_alpha for a mean depth).  A pixel no Gaussian
+     * reaches holds 0 and 0; a call that failed on the device fills both with NaN, as it does the colour.  One of the two alone
+     * is DGS_ERR_INVALID_ARGUMENT.                                                                                              */
+    float* out_depth;
+    float* out_alpha;
 } DgsRasterForwardArgs;
 
 typedef struct DgsRasterBackwardArgs {
@@ -171,7 +181,16 @@ typedef struct DgsRasterBackwardArgs {
      * 10 atomicAdd per pair; here one instruction per (tile, Gaussian) into the record) -- run-to-run differences of the order of
      * 1e-7 relative.                                                                                                            */
     void* scratch;
-    size_t scratch_bytes;
+    size_t scratch_bytes;       /* >= dgs_raster_backward_scratch_bytes(...), or dgs_raster_backward_aux_scratch_bytes(...) for an aux call */
+    /* ---- optional gradients of the aux maps (appended: a zero-initialised tail is the colour-only call) ----
+     * dL/d out_depth and dL/d out_alpha of the forward, [V,1,H,W] each; either may be NULL, which means zero.  With at least one
+     * given ("an aux call") the replay carries z as a fourth channel and a tenth per-(view, Gaussian) sum dL/dz = sum alpha_i T_i gD;
+     * dL/dalpha_i gains T_i (z_i - Drec) gD + T_final / (1 - alpha_i) gA; dL/dmeans3D gains the z row of `viewmatrix` times dL/dz,
+     * summed over the views of a set in view order; nothing flows to the cameras.  The gradients add to those of dL_dpix (which
+     * stays required: pass zeros for a loss on the maps alone).  An aux call always takes the one-pixel walk of the blend
+     * backward, and its deterministic form needs 4 more bytes of scratch per instance slot.                                  */
+    const float* dL_ddepth;
+    const float* dL_dalpha;
 } DgsRasterBackwardArgs;
 
 int dgs_abi_version(void);
@@ -190,6 +209,8 @@ int dgs_raster_backward(const DgsRasterBackwardArgs* args, dgs_stream_t stream);
 /* Bytes of DgsRasterBackwardArgs.scratch: 36 per instance slot (num_rendered as passed to the backward: the forward's count, or the
  * binning capacity of an asynchronous forward) + 20 per (view, Gaussian) + 8 per tile. */
 size_t dgs_raster_backward_scratch_bytes(int32_t P, int32_t width, int32_t height, int32_t V, int64_t num_rendered);
+/* The same for a call with dL_ddepth or dL_dalpha: 40 bytes per instance slot (the tenth sum has a slot array of its own, behind the others). */
+size_t dgs_raster_backward_aux_scratch_bytes(int32_t P, int32_t width, int32_t height, int32_t V, int64_t num_rendered);
 int dgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present, dgs_stream_t stream);
 

@@ -39,6 +39,7 @@ struct BwdParams {
     float tanfovx, tanfovy, scale_mod;
     const int* radii;
     const float* dL_dpix;
+    const float *dL_ddepth, *dL_dalpha;    // aux call (either may be null = zero): blend_backward_kernel<.., AUX = true>
     GeomState g;
     ImageState im;
     BinningState bn;
@@ -49,12 +50,13 @@ struct BwdParams {
     float4* slot_a;              // [slots]     {colour r, g, b, mean2D x}
     float4* slot_b;              // [slots]     {mean2D y, conic xx, conic xy, conic yy}
     float* slot_c;               // [slots]     opacity
+    float* slot_d;               // [slots]     z (aux calls only)
 };
 
 // Scratch of the deterministic backward, carved from ONE caller-owned buffer (dgs_raster_backward_scratch_bytes).
 struct BwdScratch {
-    uint32_t* slot_base; uint32_t* block_sums; unsigned long long* last_key; float4* slot_a; float4* slot_b; float* slot_c;
-    static BwdScratch carve(void* buf, size_t P, size_t V, size_t T, size_t slots, size_t* bytes) {
+    uint32_t* slot_base; uint32_t* block_sums; unsigned long long* last_key; float4* slot_a; float4* slot_b; float* slot_c; float* slot_d;
+    static BwdScratch carve(void* buf, size_t P, size_t V, size_t T, size_t slots, size_t* bytes, bool aux = false) {
         Carver c(buf);
         BwdScratch s;
         s.slot_base = c.take<uint32_t>(P * V + 1);
@@ -63,6 +65,7 @@ struct BwdScratch {
         s.slot_a = c.take<float4>(slots);
         s.slot_b = c.take<float4>(slots);
         s.slot_c = c.take<float>(slots);
+        s.slot_d = aux ? c.take<float>(slots) : nullptr;      // behind everything else: a call without aux carves what it always did
         if (bytes) *bytes = c.bytes();
         return s;
     }
@@ -117,10 +120,11 @@ constexpr int kAccRow = 260;
 // 1,178 us for nine instructions into four arrays with a lane per instance -- the form of rounds 1-4, whose cost inside the blend
 // kernel was 0.19 ms of 0.88 (ablation, profiles/r04_raster_backward_ablation.txt).  A wave flushes the 64 entries per 128 it staged itself
 // (it reads their ids), so no barrier separates the flush from the next batch's staging.  NPASS passes of four entries.
-template <int NPASS>
+// NV: the sums of an instance, nine, or ten in an aux call (the tenth: dL/dz, word 9 of the record).
+template <int NPASS, int NV = 9>
 __device__ __forceinline__ void flush_records(float (*acc)[kAccRow], const uint32_t* s_id, float* grad_acc, size_t vo, int first_entry, int lane) {
     const int z = lane & 15, sub = lane >> 4;
-    if (z < 9) {
+    if (z < NV) {
 #pragma unroll 4
         for (int pass = 0; pass < NPASS; ++pass) {
             const int e = first_entry + 4 * pass + sub;
@@ -148,11 +152,18 @@ __device__ __forceinline__ void flush_records(float (*acc)[kAccRow], const uint3
 // Measured per 4 views at 256^2, trained-like / random-init regime, forward + backward: one atomic per wave per value 4.14 /
 // 2.49 ms; 16 x 4 strip masks 3.45 / 2.11; + combining a tile's four strips in LDS 3.00 / 1.88; + launch order by work 2.33 /
 // 1.70; cells: see DESIGN.md.  (One wave per tile with four pixels per lane lost: a latency chain.)
-template <bool FAST_EXP, bool DET>
+//
+// AUX (DgsRasterBackwardArgs.dL_ddepth / dL_dalpha): the depth map is one more blended channel whose "colour" is the entry's z, staged behind
+// its pixel coordinates as in the forward -- so it joins the replay as a fourth channel (the accum_rec recurrence on z; a TENTH sum,
+// dL/dz = sum of alpha_i T_i gD) -- and the alpha map = 1 - final_T is the background term with the opposite sign: gA is subtracted from
+// bg . dL_dpix once per pixel, nothing per step.  This kernel only: an aux call takes the one-pixel walk (launch_blend_backward).
+template <bool FAST_EXP, bool DET, bool AUX = false>
 __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
+    using XY = typename std::conditional<AUX, float4, float2>::type;
+    constexpr int NV = AUX ? 10 : 9;
     __shared__ uint32_t s_id[256];
     __shared__ uint2 s_stat[kRasterStats ? 4 : 1];
-    __shared__ float2 s_xy[256];
+    __shared__ XY s_xy[256];
     __shared__ float4 s_co[256];
     __shared__ float4 s_rgbc[256];                        // colour, alpha cut-off on `power`
     __shared__ uint32_t s_max[4];
@@ -162,7 +173,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
     // order the four waves get there (fp32: the sum's last bit depends on that order).  Deterministic form: a copy per wave -- inside
     // a wave the adds happen in program order -- and the four copies are added in wave order when the batch is done.
     constexpr int NACC = DET ? 4 : 1;
-    __shared__ float s_acc[NACC][9][kAccRow];
+    __shared__ float s_acc[NACC][NV][kAccRow];
     const uint32_t vt = p.im.tile_order[blockIdx.x];           // order_tiles_kernel: most replayed entries first
     const int v = (int)(vt / (uint32_t)p.T), tile = (int)(vt % (uint32_t)p.T), s = v / p.vps;
     const int bx = tile % p.gx, by = tile / p.gx;
@@ -189,6 +200,11 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
     float bg_dot = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) bg_dot += p.bg[c] * dpix[c];
+    float gD = 0.f, accum_z = 0.f, last_z = 0.f;                // AUX: dL/ddepth of the pixel, the recurrence on z
+    if constexpr (AUX) {
+        if (inside && p.dL_ddepth) gD = p.dL_ddepth[(size_t)v * HW + pid];
+        if (inside && p.dL_dalpha) bg_dot -= p.dL_dalpha[(size_t)v * HW + pid];     // dalpha/dalpha_i = +T_final / (1 - alpha_i)
+    }
     float accum_rec[3] = {0.f, 0.f, 0.f}, last_color[3] = {0.f, 0.f, 0.f}, last_alpha = 0.f;
     const float ddelx_dx = (float)(0.5 * p.W), ddely_dy = (float)(0.5 * p.H);
 
@@ -200,7 +216,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
 #pragma unroll
     for (int w = 0; w < NACC; ++w)
 #pragma unroll
-        for (int k = 0; k < 9; ++k) s_acc[w][k][tid] = 0.f;
+        for (int k = 0; k < NV; ++k) s_acc[w][k][tid] = 0.f;
     __syncthreads();
     const uint32_t todo = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));   // <= rg.y - rg.x
     const int rounds = (int)((todo + 255u) / 256u);
@@ -215,8 +231,10 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
             const BlendRecord* rec = p.g.blend + vo + id;      // one line per entry (raster_state.h)
             const float4 co = rec->co;
             float4 rc = rec->rc;
-            const float2 xy = rec->xy;
-            m16 = cell_mask(xy, co, rc.w, tx0, ty0);
+            XY xy;
+            if constexpr (AUX) xy = *reinterpret_cast<const float4*>(&rec->xy);     // (x, y, z, -)
+            else xy = rec->xy;
+            m16 = cell_mask(make_float2(xy.x, xy.y), co, rc.w, tx0, ty0);
             if (colors_per_set) {
                 const float* c = p.colors_pre + 3 * ((size_t)s * p.P + id);
                 rc.x = c[0]; rc.y = c[1]; rc.z = c[2];
@@ -224,7 +242,10 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
             s_id[tid] = id; s_xy[tid] = xy; s_co[tid] = co; s_rgbc[tid] = rc;
         } else {
             // finite records in the slots without an entry (the walk reads ahead of its lists), as in the forward
-            s_id[tid] = 0u; s_xy[tid] = make_float2(0.f, 0.f); s_co[tid] = make_float4(0.f, 0.f, 0.f, 0.f); s_rgbc[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+            s_id[tid] = 0u;
+            if constexpr (AUX) s_xy[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+            else s_xy[tid] = make_float2(0.f, 0.f);
+            s_co[tid] = make_float4(0.f, 0.f, 0.f, 0.f); s_rgbc[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         unsigned long long keeps[16];
 #pragma unroll
@@ -248,7 +269,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
             const uint32_t first = todo - (uint32_t)(i * 256);          // contributor (1-based list index) of batch entry 0
             // software pipeline as in the forward: a cell's indices four at a time (one word, the next word a group ahead), the
             // entry one step ahead in two register sets that take turns; unrolled by the word: no copies, literal shifts
-            struct Entry { float2 xy; float4 co; float4 rc; };
+            struct Entry { XY xy; float4 co; float4 rc; };
             auto load = [&](uint32_t j) { return Entry{s_xy[j], s_co[j], s_rgbc[j]}; };
             auto step = [&](uint32_t k, uint32_t j, const Entry& e) {
                 // pixel took part iff index <= last_contributor (backward.cu:463-468); cheap rejects first (outside the ellipse,
@@ -270,7 +291,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
                         const float Tn = FAST_EXP ? T * inv1ma : T / (1.f - alpha);
                         const float dchannel_dcolor = alpha * Tn;
                         const float col[3] = {e.rc.x, e.rc.y, e.rc.z};
-                        float c9[9];
+                        float c9[NV];
                         float dL_dalpha = 0.0f;
 #pragma unroll
                         for (int ch = 0; ch < 3; ++ch) {
@@ -279,6 +300,13 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
                             c9[ch] = dchannel_dcolor * dpix[ch];
                             accum_rec[ch] = take ? rec : accum_rec[ch];
                             last_color[ch] = take ? col[ch] : last_color[ch];
+                        }
+                        if constexpr (AUX) {
+                            const float rec = last_alpha * last_z + (1.f - last_alpha) * accum_z;
+                            dL_dalpha += (e.xy.z - rec) * gD;
+                            c9[9] = dchannel_dcolor * gD;
+                            accum_z = take ? rec : accum_z;
+                            last_z = take ? e.xy.z : last_z;
                         }
                         dL_dalpha *= Tn;
                         dL_dalpha += (FAST_EXP ? -T_final * inv1ma : -T_final / (1.f - alpha)) * bg_dot;
@@ -296,10 +324,10 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
                         c9[8] = G * dL_dalpha;
                         const bool reduce = !(kRasterAblate && (p.ablate & 16)), add = !(kRasterAblate && (p.ablate & 2));
 #pragma unroll
-                        for (int q = 0; q < 9; ++q) c9[q] = reduce ? row_sum_to_lane15(take ? c9[q] : 0.f) : (take ? c9[q] : 0.f);
+                        for (int q = 0; q < NV; ++q) c9[q] = reduce ? row_sum_to_lane15(take ? c9[q] : 0.f) : (take ? c9[q] : 0.f);
                         if (add && (lane & 15) == 15 && ((takers >> (16 * row)) & 0xFFFFull) != 0ull) {
 #pragma unroll
-                            for (int q = 0; q < 9; ++q) lds_add(&s_acc[DET ? wave : 0][q][j], c9[q]);
+                            for (int q = 0; q < NV; ++q) lds_add(&s_acc[DET ? wave : 0][q][j], c9[q]);
                         }
                     }
                 }
@@ -321,13 +349,13 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
         }
         __syncthreads();
         if constexpr (!DET) {
-            if (!(kRasterAblate && (p.ablate & 1))) flush_records<16>(s_acc[0], s_id, p.g.grad_acc, vo, 64 * wave, lane);
+            if (!(kRasterAblate && (p.ablate & 1))) flush_records<16, NV>(s_acc[0], s_id, p.g.grad_acc, vo, 64 * wave, lane);
         } else {
             // entry `tid`: the tile's sums, stored into the slot of (Gaussian, this tile)
-            float c9[9];
+            float c9[NV];
             bool any = false;                                      // any of the four per-wave copies non-zero: from the COPIES, not from their
 #pragma unroll                                                     // sum (partials that cancel exactly would otherwise stay behind for the next batch)
-            for (int q = 0; q < 9; ++q) {
+            for (int q = 0; q < NV; ++q) {
                 const float a0 = s_acc[0][q][tid], a1 = s_acc[1][q][tid], a2 = s_acc[2][q][tid], a3 = s_acc[3][q][tid];
                 c9[q] = ((a0 + a1) + a2) + a3;
                 any = any || a0 != 0.f || a1 != 0.f || a2 != 0.f || a3 != 0.f;
@@ -339,7 +367,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
 #pragma unroll
                     for (int w = 0; w < NACC; ++w)
 #pragma unroll
-                        for (int q = 0; q < 9; ++q) s_acc[w][q][tid] = 0.f;
+                        for (int q = 0; q < NV; ++q) s_acc[w][q][tid] = 0.f;
                 }
                 const uint32_t id = s_id[tid];
                 const size_t gv = vo + id;
@@ -349,6 +377,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
                 p.slot_a[slot] = make_float4(c9[0], c9[1], c9[2], c9[3]);
                 p.slot_b[slot] = make_float4(c9[4], c9[5], c9[6], c9[7]);
                 p.slot_c[slot] = c9[8];
+                if constexpr (AUX) p.slot_d[slot] = c9[9];
             }
         }
     }
@@ -711,7 +740,7 @@ __global__ __launch_bounds__(1024) void order_tiles_kernel(const uint32_t* work,
 // Gaussian, in rectangle order (row-major), and writes the nine sums as the (view, Gaussian)'s gradient record -- what the atomic form
 // accumulates with atomics; preprocess_backward_kernel reads either.  The tiles' keys sit in LDS (8 bytes per tile): a Gaussian of the
 // random-init regime tests ~50 of them.
-template <bool LDS_KEYS>
+template <bool LDS_KEYS, bool AUX = false>
 __global__ __launch_bounds__(256) void gather_partials_kernel(BwdParams p) {
     DGS_DYNAMIC_LDS(smem);
     const int v = blockIdx.y, idx = blockIdx.x * 256 + threadIdx.x;
@@ -724,7 +753,7 @@ __global__ __launch_bounds__(256) void gather_partials_kernel(BwdParams p) {
     }
     if (idx >= p.P) return;
     const size_t gi = (size_t)v * p.P + idx;
-    float a[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float a[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // a[9]: dL/dz, aux calls only
     const int radius = p.radii[gi];
     if (radius > 0) {
         const float2 m = p.g.means2D[gi];
@@ -739,6 +768,7 @@ __global__ __launch_bounds__(256) void gather_partials_kernel(BwdParams p) {
                     a[0] += sa.x; a[1] += sa.y; a[2] += sa.z; a[3] += sa.w;
                     a[4] += sb.x; a[5] += sb.y; a[6] += sb.z; a[7] += sb.w;
                     a[8] += p.slot_c[slot];
+                    if constexpr (AUX) a[9] += p.slot_d[slot];
                 }
             }
     }
@@ -746,7 +776,7 @@ __global__ __launch_bounds__(256) void gather_partials_kernel(BwdParams p) {
         float4* rec = reinterpret_cast<float4*>(p.g.grad_acc + 16 * gi);
         rec[0] = make_float4(a[0], a[1], a[2], a[3]);
         rec[1] = make_float4(a[4], a[5], a[6], a[7]);
-        rec[2] = make_float4(a[8], 0.f, 0.f, 0.f);
+        rec[2] = make_float4(a[8], a[9], 0.f, 0.f);
     }
 }
 
@@ -754,7 +784,8 @@ __global__ __launch_bounds__(256) void gather_partials_kernel(BwdParams p) {
 // MAXM: SH coefficients the per-thread gradient array is sized for.  DiffusionGS trains degree 0 (one coefficient: `gaussians_sh_degree 0`,
 // denoiser.py:96): with the 48-float array of degree 3 the kernel needs 213 registers -- two waves per SIMD on a kernel that is a chain
 // of memory round trips; sized for what the call has it runs at twice the occupancy.
-template <int MAXM>
+// AUX: dL/dz (word 9 of the record) times the z row of the view matrix joins dL/dmeans3D; nothing flows to the cameras.
+template <int MAXM, bool AUX = false>
 __global__ __launch_bounds__(256) void preprocess_backward_kernel(BwdParams p, int S) {
     const size_t si = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (si >= (size_t)S * p.P) return;
@@ -859,6 +890,10 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(BwdParams p, i
         dmv[0] = vm[0] * dtx + vm[1] * dty + vm[2] * dtz;
         dmv[1] = vm[4] * dtx + vm[5] * dty + vm[6] * dtz;
         dmv[2] = vm[8] * dtx + vm[9] * dty + vm[10] * dtz;
+        if constexpr (AUX) {                        // p_view.z = vm[2] x + vm[6] y + vm[10] z + vm[14]
+            const float dz = p.g.grad_acc[16 * gi + 9];
+            dmv[0] += vm[2] * dz; dmv[1] += vm[6] * dz; dmv[2] += vm[10] * dz;
+        }
         // ---- preprocessCUDA backward, backward.cu:346-396 ----
         const float hw = proj[3] * mx + proj[7] * my + proj[11] * mz + proj[15];
         const float m_w = 1.0f / (hw + 0.0000001f);
@@ -957,11 +992,15 @@ static bool pair_walk(int workgroups) {
 }
 
 template <bool DET>
-static void launch_blend_backward(const BwdParams& p, int V, hipStream_t st) {
+static void launch_blend_backward(const BwdParams& p, int V, hipStream_t st, bool aux) {
     const dim3 grid((unsigned)(V * p.T));
     size_t pad = 0;                // tools' library: DGS_RASTER_BWD_LDS_PAD = bytes of unused LDS per workgroup (fewer workgroups per CU)
     if constexpr (kRasterAblate) { static const int e = [] { const char* v = getenv("DGS_RASTER_BWD_LDS_PAD"); return v ? atoi(v) : 0; }(); pad = (size_t)e; }
-    if (pair_walk<DET>(V * p.T)) {
+    if (aux) {
+        // the aux form lives in the one-pixel walk only, whatever pair_walk or DGS_RASTER_BWD_WALK say (depth and alpha maps)
+        if (p.exact_exp) hipLaunchKernelGGL((blend_backward_kernel<false, DET, true>), grid, dim3(256), pad, st, p);
+        else hipLaunchKernelGGL((blend_backward_kernel<true, DET, true>), grid, dim3(256), pad, st, p);
+    } else if (pair_walk<DET>(V * p.T)) {
         if (p.exact_exp) hipLaunchKernelGGL((blend_backward_pair_kernel<false, DET>), grid, dim3(128), pad, st, p);
         else hipLaunchKernelGGL((blend_backward_pair_kernel<true, DET>), grid, dim3(128), pad, st, p);
     } else {
@@ -970,8 +1009,13 @@ static void launch_blend_backward(const BwdParams& p, int V, hipStream_t st) {
     }
 }
 
-static void launch_preprocess_backward(const BwdParams& p, int S, size_t ns, hipStream_t st) {
+static void launch_preprocess_backward(const BwdParams& p, int S, size_t ns, hipStream_t st, bool aux) {
     const dim3 grid((unsigned)((ns + 255) / 256));
+    if (aux) {
+        if (!p.shs || (p.M == 1 && p.D == 0)) hipLaunchKernelGGL((preprocess_backward_kernel<1, true>), grid, dim3(256), 0, st, p, S);
+        else hipLaunchKernelGGL((preprocess_backward_kernel<16, true>), grid, dim3(256), 0, st, p, S);
+        return;
+    }
     // one coefficient (degree 0, or precomputed colours: no SH at all) / up to 16
     if (!p.shs || (p.M == 1 && p.D == 0)) hipLaunchKernelGGL(preprocess_backward_kernel<1>, grid, dim3(256), 0, st, p, S);
     else hipLaunchKernelGGL(preprocess_backward_kernel<16>, grid, dim3(256), 0, st, p, S);
@@ -1006,6 +1050,8 @@ extern "C" int dgs_raster_backward(const DgsRasterBackwardArgs* a, dgs_stream_t 
     p.scales = a->scales; p.rots = a->rotations; p.cov_pre = a->cov3D_precomp; p.viewm = a->viewmatrix; p.projm = a->projmatrix;
     p.campos = a->campos; p.tanfov = a->tanfov; p.tanfovx = a->tanfovx; p.tanfovy = a->tanfovy; p.scale_mod = a->scale_modifier;
     p.radii = a->radii; p.dL_dpix = a->dL_dpix;
+    p.dL_ddepth = a->dL_ddepth; p.dL_dalpha = a->dL_dalpha;
+    const bool aux = a->dL_ddepth != nullptr || a->dL_dalpha != nullptr;
     if constexpr (kRasterAblate) { static const int ab = [] { const char* e = getenv("DGS_RASTER_BWD_ABLATE"); return e ? atoi(e) : 0; }(); p.ablate = ab; }
     p.g = GeomState::carve(const_cast<void*>(a->geom_buffer), (size_t)P, (size_t)V, nullptr);
     p.im = ImageState::carve(const_cast<void*>(a->img_buffer), (size_t)W, (size_t)H, (size_t)V, nullptr);
@@ -1020,19 +1066,23 @@ extern "C" int dgs_raster_backward(const DgsRasterBackwardArgs* a, dgs_stream_t 
         // ---- deterministic form: slots instead of atomics, nothing to fill ----
         const size_t slots = (size_t)(a->num_rendered < 1 ? 1 : a->num_rendered);
         size_t need = 0;
-        const BwdScratch sc = BwdScratch::carve(a->scratch, (size_t)P, (size_t)V, (size_t)p.T, slots, &need);
+        const BwdScratch sc = BwdScratch::carve(a->scratch, (size_t)P, (size_t)V, (size_t)p.T, slots, &need, aux);
         if (a->scratch_bytes < need) return DGS_ERR_ALLOC;
-        p.slot_base = sc.slot_base; p.last_key = sc.last_key; p.slot_a = sc.slot_a; p.slot_b = sc.slot_b; p.slot_c = sc.slot_c;
+        p.slot_base = sc.slot_base; p.last_key = sc.last_key; p.slot_a = sc.slot_a; p.slot_b = sc.slot_b; p.slot_c = sc.slot_c; p.slot_d = sc.slot_d;
         const unsigned nb = (unsigned)((nv + 4095) / 4096);
         hipLaunchKernelGGL(touched_block_sums_kernel, dim3(nb), dim3(256), 0, st, p.g.tiles_touched, nv, sc.block_sums);
         hipLaunchKernelGGL(touched_scan_kernel, dim3(nb), dim3(256), 0, st, p.g.tiles_touched, nv, sc.block_sums, sc.slot_base);
         hipLaunchKernelGGL(order_tiles_kernel, dim3(1), dim3(1024), 0, st, p.im.tile_work, V * p.T, p.im.tile_order);
-        launch_blend_backward<true>(p, V, st);
+        launch_blend_backward<true>(p, V, st, aux);
         if (a->debug && hipStreamSynchronize(st) != hipSuccess) return DGS_ERR_DEVICE;
         const dim3 gridPV((unsigned)((P + 255) / 256), (unsigned)V);
-        if (p.T <= 4096) hipLaunchKernelGGL((gather_partials_kernel<true>), gridPV, dim3(256), (size_t)p.T * 8, st, p);
+        if (aux) {
+            if (p.T <= 4096) hipLaunchKernelGGL((gather_partials_kernel<true, true>), gridPV, dim3(256), (size_t)p.T * 8, st, p);
+            else hipLaunchKernelGGL((gather_partials_kernel<false, true>), gridPV, dim3(256), 0, st, p);
+        }
+        else if (p.T <= 4096) hipLaunchKernelGGL((gather_partials_kernel<true>), gridPV, dim3(256), (size_t)p.T * 8, st, p);
         else hipLaunchKernelGGL((gather_partials_kernel<false>), gridPV, dim3(256), 0, st, p);
-        launch_preprocess_backward(p, S, ns, st);
+        launch_preprocess_backward(p, S, ns, st, aux);
         if (a->debug && hipStreamSynchronize(st) != hipSuccess) return DGS_ERR_DEVICE;
         return hipGetLastError() == hipSuccess ? DGS_OK : DGS_ERR_DEVICE;
     }
@@ -1040,9 +1090,9 @@ extern "C" int dgs_raster_backward(const DgsRasterBackwardArgs* a, dgs_stream_t 
     // rasterize_points.cu:148-156); the tensors of the interface are written in full by preprocess_backward_kernel.
     if (hipMemsetAsync(p.g.grad_acc, 0, nv * 16 * sizeof(float), st) != hipSuccess) return DGS_ERR_DEVICE;
     if (a->num_rendered != 0) hipLaunchKernelGGL(order_tiles_kernel, dim3(1), dim3(1024), 0, st, p.im.tile_work, V * p.T, p.im.tile_order);
-    if (a->num_rendered != 0) launch_blend_backward<false>(p, V, st);
+    if (a->num_rendered != 0) launch_blend_backward<false>(p, V, st, aux);
     if (a->debug && hipStreamSynchronize(st) != hipSuccess) return DGS_ERR_DEVICE;
-    launch_preprocess_backward(p, S, ns, st);
+    launch_preprocess_backward(p, S, ns, st, aux);
     if (a->debug && hipStreamSynchronize(st) != hipSuccess) return DGS_ERR_DEVICE;
     return hipGetLastError() == hipSuccess ? DGS_OK : DGS_ERR_DEVICE;
 }
@@ -1052,5 +1102,13 @@ extern "C" size_t dgs_raster_backward_scratch_bytes(int32_t P, int32_t width, in
     const size_t T = (size_t)((width + kTile - 1) / kTile) * ((height + kTile - 1) / kTile);
     size_t b = 0;
     BwdScratch::carve(nullptr, (size_t)P, (size_t)V, T, (size_t)(num_rendered < 1 ? 1 : num_rendered), &b);
+    return b;
+}
+
+extern "C" size_t dgs_raster_backward_aux_scratch_bytes(int32_t P, int32_t width, int32_t height, int32_t V, int64_t num_rendered) {
+    if (P <= 0 || width <= 0 || height <= 0 || V < 1) return 0;
+    const size_t T = (size_t)((width + kTile - 1) / kTile) * ((height + kTile - 1) / kTile);
+    size_t b = 0;
+    BwdScratch::carve(nullptr, (size_t)P, (size_t)V, T, (size_t)(num_rendered < 1 ? 1 : num_rendered), &b, true);
     return b;
 }

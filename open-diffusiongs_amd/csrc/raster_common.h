@@ -1,5 +1,7 @@
 // raster_common.h -- helpers shared by the forward and backward rasterizer translation units.
 #pragma once
+#include <type_traits>
+
 #include "dgs_device.h"
 #include "raster_state.h"
 #include "dgs_raster.h"

@@ -38,6 +38,7 @@ struct FwdParams {
     int debug;               // DgsRasterForwardArgs.debug: also keeps the per-view cov3D copy in the state (inspection)
     int* radii;
     float* out_color;
+    float *out_depth, *out_alpha;     // aux maps (both or neither): blend_forward_kernel<.., AUX = true>
     GeomState g;
     ImageState im;
     BinningState bn;
@@ -170,7 +171,7 @@ __device__ __forceinline__ bool preprocess_one(const FwdParams& p, int v, int id
     BlendRecord* rec = p.g.blend + gi;
     rec->co = make_float4(conx, cony, conz, op);
     rec->rc = make_float4(rgb[0], rgb[1], rgb[2], cut);
-    rec->xy = make_float2(px, py);
+    *reinterpret_cast<float4*>(&rec->xy) = make_float4(px, py, tz, 0.f);      // xy + z + the spare word: one 16-byte store
     p.g.clamped[gi] = (uint8_t)cbits;
     p.g.tiles_touched[gi] = (uint32_t)((y1 - y0) * (x1 - x0));
     p.g.keys[0][gi] = __float_as_uint(tz);
@@ -1156,9 +1157,15 @@ __device__ __forceinline__ void scan_more(const FwdParams& p, TileScan& s, uint3
 // each lane row reading its own entry.  Per (pixel, entry) the arithmetic is the reference's, in the reference's order
 // (forward.cu:332-358); the body has no per-lane branches: one wave-uniform branch leaves when no lane passes the alpha
 // cut-off, everything behind it is selects.
-template <bool SCAN, bool FAST_EXP>
+//
+// AUX (opt-in: DgsRasterForwardArgs.out_depth / out_alpha): the entry's p_view.z is staged BEHIND its pixel coordinates -- the record's
+// (x, y, z, -) is one 16-byte read, the staged one one ds_read_b128 where the colour-only form has a b64 -- and a step makes one more
+// multiply-add of the colour's shape: depth = sum of alpha_i T_i z_i over exactly the pairs that blend into the colour; alpha = 1 -
+// final_T needs nothing per step.  The colour-only instantiations are the code they were: no LDS, register or store of this form.
+template <bool SCAN, bool FAST_EXP, bool AUX = false>
 __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
-    __shared__ float2 s_xy[256];
+    using XY = typename std::conditional<AUX, float4, float2>::type;
+    __shared__ XY s_xy[256];
     __shared__ float4 s_co[256];
     __shared__ float4 s_rgbc[256];
     __shared__ uint4 s_cnt[16];                           // [cell] entries of the batch the cell keeps, per staging wave
@@ -1189,6 +1196,7 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
     TileScan ts{0u, 0u, 0u, 0u};
     bool done = !inside;
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
+    float Dz = 0.f;                                             // AUX: un-normalised expected depth
     uint32_t last_contributor = 0;
     uint32_t st_entries = 0, st_trips = 0, st_batches = 0;      // tile_stats (measurement): per lane its cell's entries, per wave its loop trips
     for (int i = 0; i < rounds; ++i) {
@@ -1206,14 +1214,18 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
             const BlendRecord* rec = p.g.blend + vo + id;      // one line per entry (raster_state.h)
             const float4 co = rec->co;
             const float4 rc = rec->rc;
-            const float2 xy = rec->xy;
+            XY xy;
+            if constexpr (AUX) xy = *reinterpret_cast<const float4*>(&rec->xy);     // (x, y, z, -)
+            else xy = rec->xy;
             s_xy[tid] = xy; s_co[tid] = co; s_rgbc[tid] = rc;
-            m16 = cell_mask(xy, co, rc.w, tx0, ty0);
+            m16 = cell_mask(make_float2(xy.x, xy.y), co, rc.w, tx0, ty0);
         } else {
             // a slot without an entry holds a finite record: the walk reads ahead of its lists (stale indices), and the product-default
             // arithmetic multiplies a masked-out lane's colour by a zero weight instead of selecting -- 0 * NaN from LDS left by an
             // earlier kernel would poison the pixel
-            s_xy[tid] = make_float2(0.f, 0.f); s_co[tid] = make_float4(0.f, 0.f, 0.f, 0.f); s_rgbc[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (AUX) s_xy[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+            else s_xy[tid] = make_float2(0.f, 0.f);
+            s_co[tid] = make_float4(0.f, 0.f, 0.f, 0.f); s_rgbc[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         unsigned long long keeps[16];
 #pragma unroll
@@ -1244,7 +1256,7 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
             // entry itself one step ahead, in two register sets that take turns -- the loop is unrolled by the word, so there is
             // no copy between steps and every shift is a literal (the rotating form spent 13 of its ~45 VALU per step on moves)
             // (bytes behind `tot` are stale indices of earlier batches: any of them addresses a staged record, none is used)
-            struct Entry { float2 xy; float4 co; float4 rc; };
+            struct Entry { XY xy; float4 co; float4 rc; };
             auto load = [&](uint32_t j) { return Entry{s_xy[j], s_co[j], s_rgbc[j]}; };
             auto step = [&](uint32_t k, uint32_t j, const Entry& e) {
                 const float dx = e.xy.x - pfx, dy = e.xy.y - pfy;
@@ -1263,11 +1275,13 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
                         // reference's (c alpha) T products and separate adds, forward.cu:352-353, for bit-identity with the oracle)
                         const float w = blends ? alpha * T : 0.0f;
                         C0 = __builtin_fmaf(e.rc.x, w, C0); C1 = __builtin_fmaf(e.rc.y, w, C1); C2 = __builtin_fmaf(e.rc.z, w, C2);
+                        if constexpr (AUX) Dz = __builtin_fmaf(e.xy.z, w, Dz);
                     } else {
                         const float c0 = C0 + e.rc.x * alpha * T, c1 = C1 + e.rc.y * alpha * T, c2 = C2 + e.rc.z * alpha * T;
                         C0 = blends ? c0 : C0;
                         C1 = blends ? c1 : C1;
                         C2 = blends ? c2 : C2;
+                        if constexpr (AUX) { const float dz = Dz + e.xy.z * alpha * T; Dz = blends ? dz : Dz; }
                     }
                     T = blends ? test_T : T;
                     last_contributor = blends ? base + j + 1u : last_contributor;
@@ -1301,6 +1315,10 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
         out[pid] = ok ? C0 + T * p.bg[0] : bad;
         out[HW + pid] = ok ? C1 + T * p.bg[1] : bad;
         out[2 * HW + pid] = ok ? C2 + T * p.bg[2] : bad;
+        if constexpr (AUX) {                                  // [V,1,H,W] each; no background term; a pixel nothing reaches: 0, 0
+            p.out_depth[(size_t)v * HW + pid] = ok ? Dz : bad;
+            p.out_alpha[(size_t)v * HW + pid] = ok ? 1.0f - T : bad;
+        }
     }
     // how far into its list the tile got: what the backward replays, and what it ranks its launch order by
     uint32_t walked = last_contributor;
@@ -1393,9 +1411,12 @@ int dgs_raster_forward(DgsRasterForwardArgs* a, dgs_stream_t stream) {
     (void)hipGetLastError();       // hipGetLastError is sticky per thread: an unrelated earlier failure (another library's probing) must
                                    // not be reported as ours by the checks below
     if (!a->out_color || !a->geom_alloc || !a->img_alloc || !a->binning_alloc) return DGS_ERR_INVALID_ARGUMENT;
+    if ((a->out_depth == nullptr) != (a->out_alpha == nullptr)) return DGS_ERR_INVALID_ARGUMENT;    // the aux maps: both or neither
+    const bool aux = a->out_depth != nullptr;
     const size_t HW = (size_t)W * H;
     if (P == 0) {   // rasterize_points.cu:68: outputs stay zero-initialised
         hipMemsetAsync(a->out_color, 0, (size_t)V * 3 * HW * sizeof(float), st);
+        if (aux) { hipMemsetAsync(a->out_depth, 0, (size_t)V * HW * sizeof(float), st); hipMemsetAsync(a->out_alpha, 0, (size_t)V * HW * sizeof(float), st); }
         return check(st, a->debug);
     }
     if (!a->means3D || !a->opacities || !a->viewmatrix || !a->projmatrix || !a->campos || !a->background || !a->radii) return DGS_ERR_INVALID_ARGUMENT;
@@ -1410,6 +1431,7 @@ int dgs_raster_forward(DgsRasterForwardArgs* a, dgs_stream_t stream) {
     p.scales = a->scales; p.rots = a->rotations; p.cov_pre = a->cov3D_precomp; p.viewm = a->viewmatrix; p.projm = a->projmatrix;
     p.campos = a->campos; p.tanfov = a->tanfov; p.tanfovx = a->tanfovx; p.tanfovy = a->tanfovy; p.scale_mod = a->scale_modifier;
     p.prefiltered = a->prefiltered; p.raw_act = a->raw_activations; p.radii = a->radii; p.out_color = a->out_color;
+    p.out_depth = a->out_depth; p.out_alpha = a->out_alpha;
     p.exact_exp = a->exact_exp ? 1 : 0;
     p.debug = a->debug ? 1 : 0;
 
@@ -1541,7 +1563,11 @@ int dgs_raster_forward(DgsRasterForwardArgs* a, dgs_stream_t stream) {
     if ((forms & ((1 << kFormRankSort) | (1 << kFormScan))) && !radix_done) radix_sort();
     if (forms & (1 << kFormScan)) {
         hipLaunchKernelGGL(rank_rects_kernel, gridP, dim3(256), 0, st, p);
-        if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<true, false>), dim3(VT), dim3(256), blend_pad, st, p);
+        if (aux) {
+            if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<true, false, true>), dim3(VT), dim3(256), blend_pad, st, p);
+            else hipLaunchKernelGGL((blend_forward_kernel<true, true, true>), dim3(VT), dim3(256), blend_pad, st, p);
+        }
+        else if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<true, false>), dim3(VT), dim3(256), blend_pad, st, p);
         else hipLaunchKernelGGL((blend_forward_kernel<true, true>), dim3(VT), dim3(256), blend_pad, st, p);
     }
     if (forms & ((1 << kFormRankSort) | (1 << kFormBitonic))) {
@@ -1563,7 +1589,11 @@ int dgs_raster_forward(DgsRasterForwardArgs* a, dgs_stream_t stream) {
         else hipLaunchKernelGGL(tile_bitonic_kernel<256>, dim3(VT), dim3(256), lds, st, p);
     }
     if (forms & ((1 << kFormRankSort) | (1 << kFormBitonic))) {
-        if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<false, false>), dim3(VT), dim3(256), blend_pad, st, p);
+        if (aux) {
+            if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<false, false, true>), dim3(VT), dim3(256), blend_pad, st, p);
+            else hipLaunchKernelGGL((blend_forward_kernel<false, true, true>), dim3(VT), dim3(256), blend_pad, st, p);
+        }
+        else if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<false, false>), dim3(VT), dim3(256), blend_pad, st, p);
         else hipLaunchKernelGGL((blend_forward_kernel<false, true>), dim3(VT), dim3(256), blend_pad, st, p);
     }
     return check(st, a->debug);

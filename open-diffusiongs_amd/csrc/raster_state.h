@@ -54,7 +54,8 @@ struct alignas(64) BlendRecord {
     float4 co;                     // (conic.x, conic.y, conic.z, opacity)
     float4 rc;                     // (r, g, b, alpha-skip threshold on `power`)
     float2 xy;                     // pixel coordinates (also in means2D, which the binning kernels stream)
-    float2 unused;
+    float z;                       // p_view.z (also in depths): what the aux forms of the blend kernels stage behind xy, as one 16-byte read
+    float unused;
 };
 static_assert(sizeof(BlendRecord) == 64, "one record, one line");
 
@@ -73,7 +74,7 @@ struct GeomState {                 // arrays indexed [view * P + gaussian]
     uint32_t* radix_base;          // [V][256]
     uint32_t* range_ws;            // [V][range_ws_stride(P)] depth range sort (raster_forward.hip range_*_kernel)
     float* grad_acc;               // [V*P*16] backward only: the nine sums of the blend backward per (view, Gaussian) in ONE 64-byte line
-                                   //          {colour r g b, mean2D x y, conic xx xy yy, opacity, 7 unused} (raster_backward.hip)
+                                   //          {colour r g b, mean2D x y, conic xx xy yy, opacity, z (aux calls only), 6 unused} (raster_backward.hip)
     static GeomState carve(void* buf, size_t P, size_t V, size_t* bytes) {
         Carver c(buf);
         GeomState g;

@@ -34,6 +34,7 @@ class DgsRasterForwardArgs(ctypes.Structure):
         ("binning_alloc", ALLOC_FN), ("binning_user", ctypes.c_void_p),
         ("binning_capacity", ctypes.c_int64), ("num_rendered_dev", ctypes.c_void_p), ("num_rendered_host", ctypes.c_void_p), ("longest_hint", ctypes.c_int64),
         ("num_rendered", ctypes.c_int64), ("longest_list", ctypes.c_int64), ("binning_form", ctypes.c_int32), ("exact_exp", ctypes.c_int32),
+        ("out_depth", ctypes.c_void_p), ("out_alpha", ctypes.c_void_p),          # optional aux maps (NULL: the colour-only call)
     ]
 
 
@@ -54,13 +55,14 @@ class DgsRasterBackwardArgs(ctypes.Structure):
         ("dL_dcov3D", ctypes.c_void_p), ("dL_dopacity", ctypes.c_void_p), ("dL_dmeans3D", ctypes.c_void_p),
         ("dL_dsh", ctypes.c_void_p), ("dL_dscales", ctypes.c_void_p), ("dL_drotations", ctypes.c_void_p),
         ("exact_exp", ctypes.c_int32), ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
+        ("dL_ddepth", ctypes.c_void_p), ("dL_dalpha", ctypes.c_void_p),          # optional gradients of the aux maps
     ]
 
 
 # every symbol include/dgs_raster.h declares (checked by tests/test_abi.py)
 RASTER_SYMBOLS = ["dgs_abi_version", "dgs_status_string", "dgs_raster_geom_bytes", "dgs_raster_image_bytes",
                   "dgs_raster_binning_bytes", "dgs_raster_forward", "dgs_raster_binning_form", "dgs_raster_backward",
-                  "dgs_raster_backward_scratch_bytes", "dgs_mark_visible",
+                  "dgs_raster_backward_scratch_bytes", "dgs_raster_backward_aux_scratch_bytes", "dgs_mark_visible",
                   "dgs_raster_state_read", "dgs_cameras_from_c2w", "dgs_rays_from_c2w"]
 
 
@@ -83,6 +85,9 @@ def _declare(L):
         L.dgs_raster_backward.argtypes = [ctypes.POINTER(DgsRasterBackwardArgs), ctypes.c_void_p]
         L.dgs_raster_backward_scratch_bytes.restype = ctypes.c_size_t
         L.dgs_raster_backward_scratch_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
+    if hasattr(L, "dgs_raster_backward_aux_scratch_bytes"):      # absent from a build that predates the aux maps (an A/B side): raster.py refuses aux there
+        L.dgs_raster_backward_aux_scratch_bytes.restype = ctypes.c_size_t
+        L.dgs_raster_backward_aux_scratch_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
     L.dgs_mark_visible.restype = ctypes.c_int
     L.dgs_mark_visible.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.c_void_p]

@@ -43,8 +43,10 @@ def get_turntable_cameras(hfov=50, num_views=8, w=384, h=384, radius=2.7, elevat
     return w, h, num_views, fxfycxcy, np.stack(c2ws, axis=0)
 
 
-def render_turntable(pc, rendering_resolution=384, num_views=8, backend=None):
-    """gs_core.py:1203-1219: `pc` a GaussianModel -> uint8 image strip [h, v*w, 3]."""
+def render_turntable(pc, rendering_resolution=384, num_views=8, backend=None, return_aux=False):
+    """gs_core.py:1203-1219: `pc` a GaussianModel -> uint8 image strip [h, v*w, 3].
+    return_aux=True -> (strip, depth float32 [h, v*w], alpha float32 [h, v*w]) from the same render: un-normalised expected depth
+    (divide by alpha for a mean depth) and accumulated opacity."""
     from .raster import default_backend
     w, h, v, fxfycxcy, c2w = get_turntable_cameras(h=rendering_resolution, w=rendering_resolution, num_views=num_views)
     dev = pc._xyz.device
@@ -53,14 +55,19 @@ def render_turntable(pc, rendering_resolution=384, num_views=8, backend=None):
     be = backend if backend is not None else default_backend()
     feats = pc.get_features.float()[None]
     r = be.render_views(pc._xyz.float()[None], feats, pc._scaling.float()[None], pc._rotation.float()[None], pc._opacity.float()[None],
-                        h, w, c, k)[0]                                   # [v, 3, h, w]
+                        h, w, c, k, **(dict(aux=True) if return_aux else {}))
+    r, maps = (r[0][0], [m[0, :, 0].detach().cpu().numpy() for m in r[1:]]) if return_aux else (r[0], None)   # [v, 3, h, w]; [v, h, w] x 2
     r = (r.detach().cpu().numpy() * 255).clip(0, 255).astype(np.uint8)
-    return np.ascontiguousarray(r.transpose(2, 0, 3, 1).reshape(h, v * w, 3))       # "v c h w -> h (v w) c"
+    strip = np.ascontiguousarray(r.transpose(2, 0, 3, 1).reshape(h, v * w, 3))      # "v c h w -> h (v w) c"
+    if return_aux:
+        return (strip,) + tuple(np.ascontiguousarray(m.transpose(1, 0, 2).reshape(h, v * w)) for m in maps)
+    return strip
 
 
-def render_generic(pc, c2ws, fxfycxcy, h=512, w=512, backend=None):
+def render_generic(pc, c2ws, fxfycxcy, h=512, w=512, backend=None, return_aux=False):
     """gs_core.py:1300-1316: `pc` a GaussianModel, c2ws [v, 4, 4], fxfycxcy [v, 4] -> uint8 [v, h, w, 3].  The reference loops
-    render_opencv_cam over the views; here they are one batched launch sequence."""
+    render_opencv_cam over the views; here they are one batched launch sequence.
+    return_aux=True -> (images, depth float32 [v, h, w], alpha float32 [v, h, w]) from the same render."""
     from .raster import default_backend
     dev = pc._xyz.device
     c = torch.as_tensor(c2ws).float().to(dev)[None]
@@ -68,9 +75,11 @@ def render_generic(pc, c2ws, fxfycxcy, h=512, w=512, backend=None):
     be = backend if backend is not None else default_backend()
     with torch.no_grad():
         r = be.render_views(pc._xyz.float()[None], pc.get_features.float()[None], pc._scaling.float()[None], pc._rotation.float()[None],
-                            pc._opacity.float()[None], h, w, c, k)[0]                       # [v, 3, h, w]
+                            pc._opacity.float()[None], h, w, c, k, **(dict(aux=True) if return_aux else {}))
+    r, maps = (r[0][0], [m[0, :, 0].detach().cpu().numpy() for m in r[1:]]) if return_aux else (r[0], None)   # [v, 3, h, w]; [v, h, w] x 2
     r = (r.detach().cpu().numpy() * 255).clip(0, 255).astype(np.uint8)
-    return np.ascontiguousarray(r.transpose(0, 2, 3, 1))                                   # "v c h w -> v h w c"
+    img = np.ascontiguousarray(r.transpose(0, 2, 3, 1))                                    # "v c h w -> v h w c"
+    return (img,) + tuple(maps) if return_aux else img
 
 
 def construct_dtypes(pc, enable_gs_viewer=True):

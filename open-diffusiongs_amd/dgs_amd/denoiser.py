@@ -165,7 +165,9 @@ class GaussianModel:
 
 
 class Renderer(nn.Module):
-    """renderer.py:20-92.  forward(...) -> [b, v, 3, H, W] float32; all b*v views in one launch sequence."""
+    """renderer.py:20-92.  forward(...) -> [b, v, 3, H, W] float32; all b*v views in one launch sequence.
+    return_aux=True -> (renderings, depth [b, v, 1, H, W], alpha [b, v, 1, H, W]): the tuple the reference's scene path carries
+    (gs_core.py:1106-1145, always zero there), from the same render; differentiable when the colour is."""
 
     def __init__(self, config, backend=None):
         super().__init__()
@@ -177,15 +179,15 @@ class Renderer(nn.Module):
     def backend(self):
         return self._backend if self._backend is not None else default_backend()
 
-    def forward(self, xyz, features, scaling, rotation, opacity, height, width, C2W, fxfycxcy, deferred=True):
+    def forward(self, xyz, features, scaling, rotation, opacity, height, width, C2W, fxfycxcy, deferred=True, return_aux=False):
         f = lambda t: t.float()      # custom_fwd(cast_inputs=float32), renderer.py:34
         backend = self.backend()
         if torch.is_grad_enabled() and any(t.requires_grad for t in (xyz, features, scaling, rotation, opacity)):
             from .raster import render_views_autograd      # training: DeferredGaussianRender's role, gs_core.py:949-1064
             return render_views_autograd(backend, f(xyz), f(features), f(scaling), f(rotation), f(opacity), height, width,
-                                         f(C2W), f(fxfycxcy))
+                                         f(C2W), f(fxfycxcy), **(dict(aux=True) if return_aux else {}))
         return backend.render_views(f(xyz), f(features), f(scaling), f(rotation), f(opacity), height, width,
-                                              f(C2W), f(fxfycxcy))
+                                              f(C2W), f(fxfycxcy), **(dict(aux=True) if return_aux else {}))
 
 
 SceneRenderer = Renderer
@@ -499,9 +501,11 @@ class DGSDenoiser(nn.Module):
             aligned.clamp_(-1.0, 1.0)
         return AttrDict(out), aligned
 
-    def render_gaussians(self, gaussian_params, c2w, fxfycxcy, height, width):   # denoiser.py:420-434
+    def render_gaussians(self, gaussian_params, c2w, fxfycxcy, height, width, return_aux=False):   # denoiser.py:420-434
+        """return_aux=True -> (renderings, depth, alpha), see Renderer."""
         return self.gs_renderer(gaussian_params.xyz, gaussian_params.features, gaussian_params.scaling,
-                                gaussian_params.rotation, gaussian_params.opacity, height, width, C2W=c2w, fxfycxcy=fxfycxcy)
+                                gaussian_params.rotation, gaussian_params.opacity, height, width, C2W=c2w, fxfycxcy=fxfycxcy,
+                                **(dict(return_aux=True) if return_aux else {}))
 
     @property
     def dtype(self):

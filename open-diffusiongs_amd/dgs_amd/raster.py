@@ -199,15 +199,20 @@ class RasterBackend:
 
     def forward_views(self, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                       viewmatrix, projmatrix, campos, tanfov, tanfovx, tanfovy, image_height, image_width, sh, degree,
-                      prefiltered, debug, views_per_set=1, raw_activations=False, binning_capacity=0, planned=False, forward_only=False):
+                      prefiltered, debug, views_per_set=1, raw_activations=False, binning_capacity=0, planned=False, forward_only=False,
+                      aux=False):
         """Batched entry: means3D [S,P,3] (other per-Gaussian inputs [S,P,...]); viewmatrix/projmatrix [V,4,4];
         campos [V,3]; tanfov optional [V,2] tensor.  Returns (num_rendered, color[V,3,H,W], radii[V,P], geom, binning, img).
+        aux=True: the same tuple + (depth[V,1,H,W], alpha[V,1,H,W]) -- alpha = 1 - final_T, depth = sum alpha_i T_i z_i, un-normalised,
+        no background term (dgs_raster.h `out_depth`), written by the same blend pass (a re-render of an outgrown plan included).
         planned=True (the product's render path: Renderer.forward): no host synchronisation -- the binning capacity and the ordering
         form come from the `_AsyncPlan` of this shape; the FIRST call of a shape runs the synchronous form to learn them.  The
         returned `num_rendered` is then the capacity the binning buffer was carved with (what the backward takes); a scene that
         outgrows the plan is rendered again before the call returns (`_AsyncPlan`), never reported as NaN.  forward_only=True: no
         backward will take this call's state, so the buffer may be sized for the worst case within the plan's budget."""
         device = means3D.device
+        if aux and not hasattr(self.lib, "dgs_raster_backward_aux_scratch_bytes"):
+            raise RuntimeError("dgs rasterizer: this build of the library predates the depth / alpha maps -- rebuild it (`python -m dgs_amd.build`)")
         S, P = int(means3D.shape[0]), int(means3D.shape[1])
         V = int(viewmatrix.shape[0])
         H, W = int(image_height), int(image_width)
@@ -226,8 +231,9 @@ class RasterBackend:
         holder = {"geom": torch.empty(0, dtype=torch.uint8, device=device),
                   "binning": torch.empty(0, dtype=torch.uint8, device=device),
                   "img": torch.empty(0, dtype=torch.uint8, device=device)}
+        maps = (alloc((V, 1, H, W), dtype=torch.float32, device=device), alloc((V, 1, H, W), dtype=torch.float32, device=device)) if aux else ()
         if P == 0:
-            return 0, out_color, radii, holder["geom"], holder["binning"], holder["img"]
+            return (0, out_color, radii, holder["geom"], holder["binning"], holder["img"]) + maps
         a = _native.DgsRasterForwardArgs()
         a.P, a.D, a.M, a.width, a.height, a.V, a.views_per_set = P, int(degree), M, W, H, V, int(views_per_set)
         a.background = _ptr(keep["bg"]); a.means3D = _ptr(means3D); a.shs = _ptr(keep["sh"])
@@ -238,6 +244,8 @@ class RasterBackend:
         a.prefiltered, a.debug, a.raw_activations = int(bool(prefiltered)), int(bool(debug)), int(bool(raw_activations))
         a.out_color = ctypes.c_void_p(out_color.data_ptr())
         a.radii = ctypes.c_void_p(radii.data_ptr())
+        if aux:
+            a.out_depth, a.out_alpha = ctypes.c_void_p(maps[0].data_ptr()), ctypes.c_void_p(maps[1].data_ptr())
         cbs = [self._allocator(holder, k, device) for k in ("geom", "img", "binning")]
         a.geom_alloc, a.img_alloc, a.binning_alloc = cbs
         a.binning_form = int(os.environ.get("DGS_RASTER_BIN", "0") or 0)     # tests / measurement only (dgs_raster.h)
@@ -281,10 +289,10 @@ class RasterBackend:
                     plan.note(self.lib, int(a.num_rendered), int(a.longest_list), P, W, H, V)
                     if device.type == "cuda":
                         plan.host_words(for_graph=True)   # the pinned words exist before anybody captures a call of this shape
-                return int(a.num_rendered), out_color, radii, holder["geom"], holder["binning"], holder["img"]
+                return (int(a.num_rendered), out_color, radii, holder["geom"], holder["binning"], holder["img"]) + maps
             if plan is None:                          # a caller with a capacity of its own: the four words are its business
                 self.last_async_stats = ndev
-                return int(binning_capacity), out_color, radii, holder["geom"], holder["binning"], holder["img"]
+                return (int(binning_capacity), out_color, radii, holder["geom"], holder["binning"], holder["img"]) + maps
             plan.calls["async"] += 1
             if capturing:
                 # rewritten by every replay; the graph's owner (dgs_amd/graph.py) verifies each replay of a plan at risk
@@ -323,7 +331,7 @@ class RasterBackend:
             plan.calls["healed"] += 1                 # the buffer was too small: again, now sized for this scene (same stream, same outputs)
         else:
             raise RuntimeError("dgs rasterizer: a render kept outgrowing its binning buffer")
-        return int(binning_capacity), out_color, radii, holder["geom"], holder["binning"], holder["img"]
+        return (int(binning_capacity), out_color, radii, holder["geom"], holder["binning"], holder["img"]) + maps
 
     # -- captured calls: the owner of a graph hands out the pinned rows its calls report into and learns which plans they used ----
     def begin_capture_log(self, rows=None):
@@ -359,10 +367,11 @@ class RasterBackend:
 
     def backward_views(self, background, means3D, radii, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                        viewmatrix, projmatrix, campos, tanfov, tanfovx, tanfovy, dL_dpix, sh, degree, geom, num_rendered,
-                       binning, img, debug, views_per_set=1, raw_activations=False):
+                       binning, img, debug, views_per_set=1, raw_activations=False, grad_depth=None, grad_alpha=None):
         """Batched backward: means3D [S,P,3], radii [V,P], dL_dpix [V,3,H,W] -> dict of gradients
         (means2D [V,P,3], cov3D [V,P,6] per view; means3D, opacity, scales, rotations, sh (and colors when precomputed)
-        summed over the views of each set)."""
+        summed over the views of each set).  grad_depth / grad_alpha [V,1,H,W]: gradients of the aux maps of `forward_views(aux=True)`,
+        added to those of dL_dpix in the same launch sequence; None = zero (dgs_raster.h `dL_ddepth`)."""
         device = means3D.device
         S, P = int(means3D.shape[0]), int(means3D.shape[1])
         V = int(viewmatrix.shape[0])
@@ -370,7 +379,14 @@ class RasterBackend:
         keep = dict(bg=_prep(background, device), means=_prep(means3D, device), colors=_prep(colors, device),
                     op=_prep(opacity, device), scales=_prep(scales, device), rots=_prep(rotations, device),
                     cov=_prep(cov3D_precomp, device), vm=_prep(viewmatrix, device), pm=_prep(projmatrix, device),
-                    cam=_prep(campos, device), sh=_prep(sh, device), tanfov=_prep(tanfov, device), g=_prep(dL_dpix, device))
+                    cam=_prep(campos, device), sh=_prep(sh, device), tanfov=_prep(tanfov, device), g=_prep(dL_dpix, device),
+                    gd=_prep(grad_depth, device), ga=_prep(grad_alpha, device))
+        for k in ("gd", "ga"):
+            if keep[k] is not None and keep[k].numel() != V * H * W:
+                raise RuntimeError(f"dgs rasterizer: grad_depth / grad_alpha must be [V,1,H,W] = [{V},1,{H},{W}], got {tuple(keep[k].shape)}")
+        aux = keep["gd"] is not None or keep["ga"] is not None
+        if aux and not hasattr(self.lib, "dgs_raster_backward_aux_scratch_bytes"):
+            raise RuntimeError("dgs rasterizer: this build of the library predates the depth / alpha maps -- rebuild it (`python -m dgs_amd.build`)")
         M = int(keep["sh"].shape[-2]) if keep["sh"] is not None else 0
         use_sr = keep["cov"] is None
         # ONE allocation for every gradient, no fill from here: the library zeroes the four tensors it accumulates into (laid out
@@ -404,9 +420,11 @@ class RasterBackend:
         a.dL_dsh = _ptr(out["sh"]) if M else None
         a.dL_dscales, a.dL_drotations = (_ptr(out["scales"]), _ptr(out["rotations"])) if use_sr else (None, None)
         a.exact_exp = int(self.exact_exp)
+        a.dL_ddepth, a.dL_dalpha = _ptr(keep["gd"]), _ptr(keep["ga"])
         scratch = None
         if self.deterministic and int(num_rendered) > 0:
-            nbytes = int(self.lib.dgs_raster_backward_scratch_bytes(P, W, H, V, int(num_rendered)))
+            size_fn = self.lib.dgs_raster_backward_aux_scratch_bytes if aux else self.lib.dgs_raster_backward_scratch_bytes
+            nbytes = int(size_fn(P, W, H, V, int(num_rendered)))
             budget = self.deterministic_budget
             if device.type == "cuda":
                 # ... and never more than 80 % of what the device can still give (free memory + what torch's allocator holds unused:
@@ -452,10 +470,11 @@ class RasterBackend:
         shape = lead + (3, int(height), int(width))
         return ray_o.reshape(shape), ray_d.reshape(shape)
 
-    def render_views(self, xyz, features, scaling, rotation, opacity, height, width, c2w, fxfycxcy, bg=None):
+    def render_views(self, xyz, features, scaling, rotation, opacity, height, width, c2w, fxfycxcy, bg=None, aux=False):
         """Forward-only batched render of RAW Gaussian parameters (what Renderer.forward / deferred_gaussian_render do
         per (sample, view) in the reference, renderer.py:34-92, gs_core.py:874-1016): xyz [B,P,3], features [B,P,M,3],
-        scaling/rotation/opacity raw [B,P,3|4|1]; c2w [B,V,4,4]; fxfycxcy [B,V,4] -> [B,V,3,H,W] float32."""
+        scaling/rotation/opacity raw [B,P,3|4|1]; c2w [B,V,4,4]; fxfycxcy [B,V,4] -> [B,V,3,H,W] float32.
+        aux=True -> (color [B,V,3,H,W], depth [B,V,1,H,W], alpha [B,V,1,H,W]), the shapes of gs_core.py:1106-1115."""
         device = xyz.device
         B, V = int(c2w.shape[0]), int(c2w.shape[1])
         view, proj, campos, tanfov = self.cameras_from_c2w(c2w, fxfycxcy, height, width)
@@ -465,7 +484,10 @@ class RasterBackend:
         degree = int(round(M ** 0.5)) - 1
         out = self.forward_views(bg, xyz, None, opacity.reshape(B, -1), scaling, rotation, 1.0, None, view, proj, campos,
                                  tanfov, 0.0, 0.0, height, width, features, degree, False, False, views_per_set=V,
-                                 raw_activations=True, planned=True, forward_only=True)
+                                 raw_activations=True, planned=True, forward_only=True, aux=aux)
+        if aux:
+            return (out[1].reshape(B, V, 3, int(height), int(width)), out[6].reshape(B, V, 1, int(height), int(width)),
+                    out[7].reshape(B, V, 1, int(height), int(width)))
         return out[1].reshape(B, V, 3, int(height), int(width))
 
     # -- _C.mark_visible ------------------------------------------------------------------
@@ -498,7 +520,7 @@ class _RenderViews(torch.autograd.Function):
     buffers are kept for backward (no second forward pass: MI355X has the HBM for it)."""
 
     @staticmethod
-    def forward(ctx, backend, xyz, features, scaling, rotation, opacity, c2w, fxfycxcy, height, width, bg):
+    def forward(ctx, backend, xyz, features, scaling, rotation, opacity, c2w, fxfycxcy, height, width, bg, aux):
         device = xyz.device
         B, V = int(c2w.shape[0]), int(c2w.shape[1])
         view, proj, campos, tanfov = backend.cameras_from_c2w(c2w, fxfycxcy, height, width)
@@ -506,29 +528,43 @@ class _RenderViews(torch.autograd.Function):
         degree = int(round(M ** 0.5)) - 1
         f = lambda t: t.detach().to(torch.float32).contiguous()
         xyz_, sh_, sc_, ro_, op_ = f(xyz), f(features), f(scaling), f(rotation), f(opacity).reshape(B, -1)
-        n, color, radii, geom, binning, img = backend.forward_views(
+        out = backend.forward_views(
             bg, xyz_, None, op_, sc_, ro_, 1.0, None, view, proj, campos, tanfov, 0.0, 0.0, height, width, sh_, degree,
-            False, False, views_per_set=V, raw_activations=True, planned=True)
-        ctx.backend, ctx.meta = backend, (B, V, int(height), int(width), degree, n)
+            False, False, views_per_set=V, raw_activations=True, planned=True, aux=aux)
+        n, color, radii, geom, binning, img = out[:6]
+        ctx.backend, ctx.meta, ctx.aux = backend, (B, V, int(height), int(width), degree, n), bool(aux)
         ctx.save_for_backward(bg, xyz_, sh_, sc_, ro_, op_, view, proj, campos, tanfov, radii, geom, binning, img)
+        if aux:
+            ctx.set_materialize_grads(False)            # a map nobody took a gradient of arrives as None = absent, not as a tensor of zeros
+            return (color.reshape(B, V, 3, int(height), int(width)), out[6].reshape(B, V, 1, int(height), int(width)),
+                    out[7].reshape(B, V, 1, int(height), int(width)))
         return color.reshape(B, V, 3, int(height), int(width))
 
     @staticmethod
-    def backward(ctx, grad):
+    def backward(ctx, grad, grad_depth=None, grad_alpha=None):
         bg, xyz_, sh_, sc_, ro_, op_, view, proj, campos, tanfov, radii, geom, binning, img = ctx.saved_tensors
         B, V, H, W, degree, n = ctx.meta
+        kw = {}
+        if ctx.aux:
+            if grad is None:
+                if grad_depth is None and grad_alpha is None:
+                    return (None,) * 12
+                grad = torch.zeros((B * V, 3, H, W), dtype=torch.float32, device=xyz_.device)
+            kw = dict(grad_depth=None if grad_depth is None else grad_depth.reshape(B * V, 1, H, W),
+                      grad_alpha=None if grad_alpha is None else grad_alpha.reshape(B * V, 1, H, W))
         g = ctx.backend.backward_views(bg, xyz_, radii, None, op_, sc_, ro_, 1.0, None, view, proj, campos, tanfov, 0.0, 0.0,
                                        grad.reshape(B * V, 3, H, W), sh_, degree, geom, n, binning, img, False,
-                                       views_per_set=V, raw_activations=True)
+                                       views_per_set=V, raw_activations=True, **kw)
         return (None, g["means3D"], g["sh"], g["scales"], g["rotations"], g["opacity"].reshape(B, -1, 1), None, None, None,
-                None, None)
+                None, None, None)
 
 
-def render_views_autograd(backend, xyz, features, scaling, rotation, opacity, height, width, c2w, fxfycxcy, bg=None):
-    """[B,P,..] raw Gaussian parameters -> [B,V,3,H,W]; differentiable w.r.t. the five parameter tensors."""
+def render_views_autograd(backend, xyz, features, scaling, rotation, opacity, height, width, c2w, fxfycxcy, bg=None, aux=False):
+    """[B,P,..] raw Gaussian parameters -> [B,V,3,H,W]; differentiable w.r.t. the five parameter tensors.
+    aux=True -> (color, depth [B,V,1,H,W], alpha [B,V,1,H,W]): all three differentiable, through ONE backward call."""
     if bg is None:
         bg = _white(xyz.device)
-    return _RenderViews.apply(backend, xyz, features, scaling, rotation, opacity, c2w.float(), fxfycxcy.float(), height, width, bg)
+    return _RenderViews.apply(backend, xyz, features, scaling, rotation, opacity, c2w.float(), fxfycxcy.float(), height, width, bg, bool(aux))
 
 
 _default = None
