@@ -14,6 +14,8 @@
 //                                                              of <= 256 x 9; the replay starts at the tile's deepest
 //                                                              contributor.  blend_backward_pair_kernel: the same with two
 //                                                              pixels per lane (packed fp32), for grids of >= 3,072 tiles
+//                                                              (staging, per-cell lists and the pipelined walk: the forward's,
+//                                                              raster_cells.h)
 //                                                            DETERMINISTIC form (DgsRasterBackwardArgs.scratch, opt-in):
 //                                                              no atomic at all.  A (tile, Gaussian) instance has a slot
 //                                                              of its own, Gaussian-major -- slot = (exclusive scan of
@@ -29,7 +31,7 @@
 //     computeCov3D :278-341)                                   set are summed in registers in a fixed order -- no atomics,
 //   torch autograd of exp / normalize / sigmoid                deterministic -- and the activation Jacobians are applied in
 //     (gs_core.py:330-334) when raw_activations = 1            the same pass
-#include "raster_common.h"
+#include "raster_cells.h"
 
 namespace dgs {
 
@@ -138,11 +140,23 @@ __device__ __forceinline__ void flush_records(float (*acc)[kAccRow], const uint3
     __builtin_amdgcn_wave_barrier();      // the wave's next staging overwrites the ids its other lanes read here (no instruction on the GPU)
 }
 
+// Stages entry e of a batch of the replay -- the list's entry `idx` (from `list_begin` in point_list), none if idx < 0 -- with its id
+// (the flush and the slot store read it) and the colours of set s when they are per set: stage_entry, raster_cells.h.
+template <bool AUX>
+__device__ __forceinline__ unsigned stage_replayed(const BwdParams& p, uint32_t list_begin, int idx, int e, size_t vo, int s, float tx0, float ty0,
+                                                   uint32_t (&s_id)[256], CellXY<AUX> (&s_xy)[256], float4 (&s_co)[256], float4 (&s_rgbc)[256]) {
+    const bool has = idx >= 0;
+    const uint32_t id = has ? p.bn.point_list[list_begin + (uint32_t)idx] : 0u;
+    s_id[e] = id;
+    const float* colors = p.colors_pre ? p.colors_pre + 3 * (size_t)s * p.P : nullptr;
+    return stage_entry<AUX>(has, p.g.blend + vo, colors, id, e, tx0, ty0, s_xy, s_co, s_rgbc);
+}
+
 // grid V*T (workgroup b takes tile tile_order[b]), 256 threads = 4 wave64.  backward.cu:399-557.
 //
 // Lanes, pixels and lists as in the forward (blend_forward_kernel): wave g owns strip g, its four 16-lane rows own the strip's
-// four 4 x 4 cells; a batch of 256 list entries is staged in LDS back to front, compacted into one index list per cell
-// (cell_mask: the cells the Gaussian's ellipse can reach), and the four rows of a wave walk their lists in lockstep.
+// four 4 x 4 cells; the list goes through the same cell-list mechanism (raster_cells.h: stage_entry, compact_cells, walk_cell),
+// back to front, and the four rows of a wave walk their lists in lockstep.
 //
 // Per (tile, Gaussian) the nine sums have to be reduced over up to 256 pixels.  A 16-lane row reduces its cell with four DPP
 // adds per value; lane 15 of the row adds the nine partial sums into the batch entry's accumulators in LDS (ds_add_f32: up
@@ -159,11 +173,10 @@ __device__ __forceinline__ void flush_records(float (*acc)[kAccRow], const uint3
 // bg . dL_dpix once per pixel, nothing per step.  This kernel only: an aux call takes the one-pixel walk (launch_blend_backward).
 template <bool FAST_EXP, bool DET, bool AUX = false>
 __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
-    using XY = typename std::conditional<AUX, float4, float2>::type;
     constexpr int NV = AUX ? 10 : 9;
     __shared__ uint32_t s_id[256];
     __shared__ uint2 s_stat[kRasterStats ? 4 : 1];
-    __shared__ XY s_xy[256];
+    __shared__ CellXY<AUX> s_xy[256];
     __shared__ float4 s_co[256];
     __shared__ float4 s_rgbc[256];                        // colour, alpha cut-off on `power`
     __shared__ uint32_t s_max[4];
@@ -220,56 +233,15 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
     __syncthreads();
     const uint32_t todo = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));   // <= rg.y - rg.x
     const int rounds = (int)((todo + 255u) / 256u);
-    const bool colors_per_set = p.colors_pre != nullptr;
     uint32_t st_entries = 0, st_trips = 0;                      // tile_stats (measurement)
     for (int i = 0; i < rounds; ++i) {
         // batch entry e (0..255) = 1-based list index contributor = todo - (i * 256 + e), list position rg.x + contributor - 1
         const int idx = (int)todo - 1 - (i * 256 + tid);
-        unsigned m16 = 0u;
-        if (idx >= 0) {
-            const uint32_t id = p.bn.point_list[rg.x + (uint32_t)idx];
-            const BlendRecord* rec = p.g.blend + vo + id;      // one line per entry (raster_state.h)
-            const float4 co = rec->co;
-            float4 rc = rec->rc;
-            XY xy;
-            if constexpr (AUX) xy = *reinterpret_cast<const float4*>(&rec->xy);     // (x, y, z, -)
-            else xy = rec->xy;
-            m16 = cell_mask(make_float2(xy.x, xy.y), co, rc.w, tx0, ty0);
-            if (colors_per_set) {
-                const float* c = p.colors_pre + 3 * ((size_t)s * p.P + id);
-                rc.x = c[0]; rc.y = c[1]; rc.z = c[2];
-            }
-            s_id[tid] = id; s_xy[tid] = xy; s_co[tid] = co; s_rgbc[tid] = rc;
-        } else {
-            // finite records in the slots without an entry (the walk reads ahead of its lists), as in the forward
-            s_id[tid] = 0u;
-            if constexpr (AUX) s_xy[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-            else s_xy[tid] = make_float2(0.f, 0.f);
-            s_co[tid] = make_float4(0.f, 0.f, 0.f, 0.f); s_rgbc[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        unsigned long long keeps[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            keeps[c] = __ballot((m16 >> c) & 1u);
-            if (lane == 0) reinterpret_cast<uint32_t*>(&s_cnt[c])[wave] = (uint32_t)__popcll(keeps[c]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            if ((m16 >> c) & 1u) {
-                const uint4 cn = s_cnt[c];
-                const uint32_t ahead = (wave > 0 ? cn.x : 0u) + (wave > 1 ? cn.y : 0u) + (wave > 2 ? cn.z : 0u);
-                s_list[c][ahead + (uint32_t)__popcll(keeps[c] & lanes_before)] = (uint8_t)tid;
-            }
-        }
-        __syncthreads();
+        const unsigned m16[1] = {stage_replayed<AUX>(p, rg.x, idx, tid, vo, s, tx0, ty0, s_id, s_xy, s_co, s_rgbc)};
         {
-            const uint4 cn = s_cnt[cell];
-            const uint32_t tot = cn.x + cn.y + cn.z + cn.w;
+            const uint32_t tot = compact_cells<1>(m16, cell, tid, lane, wave, lanes_before, s_cnt, s_list);
             const uint32_t first = todo - (uint32_t)(i * 256);          // contributor (1-based list index) of batch entry 0
-            // software pipeline as in the forward: a cell's indices four at a time (one word, the next word a group ahead), the
-            // entry one step ahead in two register sets that take turns; unrolled by the word: no copies, literal shifts
-            struct Entry { XY xy; float4 co; float4 rc; };
+            using Entry = CellEntry<AUX>;
             auto load = [&](uint32_t j) { return Entry{s_xy[j], s_co[j], s_rgbc[j]}; };
             auto step = [&](uint32_t k, uint32_t j, const Entry& e) {
                 // pixel took part iff index <= last_contributor (backward.cu:463-468); cheap rejects first (outside the ellipse,
@@ -332,75 +304,23 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(BwdParams p) {
                     }
                 }
             };
-            const uint32_t* lst = reinterpret_cast<const uint32_t*>(s_list[cell]);
-            uint32_t word = lst[0];
-            Entry ea = load(word & 255u), eb;
-            if constexpr (kRasterStats) st_entries += tot;
-            uint32_t k = 0;
-            for (; wave_ballot(k < tot) != 0ull && !(kRasterAblate && (p.ablate & 4)); k += 4) {
-                const uint32_t word_next = lst[(k >> 2) + 1u];
-                eb = load((word >> 8) & 255u);  step(k, word & 255u, ea);
-                ea = load((word >> 16) & 255u); step(k + 1u, (word >> 8) & 255u, eb);
-                eb = load(word >> 24);          step(k + 2u, (word >> 16) & 255u, ea);
-                ea = load(word_next & 255u);    step(k + 3u, word >> 24, eb);
-                word = word_next;
-            }
-            if constexpr (kRasterStats) st_trips += k;
+            const uint32_t k = walk_cell(s_list[cell], load, step,
+                                         [&](uint32_t at) { return wave_ballot(at < tot) != 0ull && !(kRasterAblate && (p.ablate & 4)); });
+            if constexpr (kRasterStats) { st_entries += tot; st_trips += k; }
         }
         __syncthreads();
         if constexpr (!DET) {
             if (!(kRasterAblate && (p.ablate & 1))) flush_records<16, NV>(s_acc[0], s_id, p.g.grad_acc, vo, 64 * wave, lane);
         } else {
-            // entry `tid`: the tile's sums, stored into the slot of (Gaussian, this tile)
-            float c9[NV];
-            bool any = false;                                      // any of the four per-wave copies non-zero: from the COPIES, not from their
-#pragma unroll                                                     // sum (partials that cancel exactly would otherwise stay behind for the next batch)
-            for (int q = 0; q < NV; ++q) {
-                const float a0 = s_acc[0][q][tid], a1 = s_acc[1][q][tid], a2 = s_acc[2][q][tid], a3 = s_acc[3][q][tid];
-                c9[q] = ((a0 + a1) + a2) + a3;
-                any = any || a0 != 0.f || a1 != 0.f || a2 != 0.f || a3 != 0.f;
-            }
-            // every replayed entry STORES its sums (zeros too): Gaussian-major, the tile's index inside the Gaussian's rectangle (the
-            // forward's tile_rect on the same state: the same rectangle)
-            if (idx >= 0) {
-                if (any) {
-#pragma unroll
-                    for (int w = 0; w < NACC; ++w)
-#pragma unroll
-                        for (int q = 0; q < NV; ++q) s_acc[w][q][tid] = 0.f;
-                }
-                const uint32_t id = s_id[tid];
-                const size_t gv = vo + id;
-                int x0, y0, x1, y1;
-                tile_rect(s_xy[tid].x, s_xy[tid].y, p.radii[gv], p.gx, p.gy, &x0, &y0, &x1, &y1);
-                const size_t slot = (size_t)p.slot_base[gv] + (size_t)((by - y0) * (x1 - x0) + (bx - x0));
-                p.slot_a[slot] = make_float4(c9[0], c9[1], c9[2], c9[3]);
-                p.slot_b[slot] = make_float4(c9[4], c9[5], c9[6], c9[7]);
-                p.slot_c[slot] = c9[8];
-                if constexpr (AUX) p.slot_d[slot] = c9[9];
-            }
+            store_slots(p, s_acc, s_id, s_xy, tid, idx >= 0, vo, bx, by);
         }
     }
     if constexpr (DET) {
-        // what this tile replayed: the first `todo` entries of its list, which is sorted by (depth bits, Gaussian index)
-        if (tid == 0) {
-            unsigned long long key = 0ull;
-            if (todo > 0) {
-                const uint32_t id = p.bn.point_list[rg.x + todo - 1u];
-                key = ((unsigned long long)__float_as_uint(p.g.depths[vo + id]) << 32) | id;
-            }
-            p.last_key[vt] = key;
-        }
+        if (tid == 0) write_last_key(p, vt, rg.x, todo, vo);
     }
     if constexpr (kRasterStats) {
-        uint32_t ent = (lane & 15) == 0 ? st_entries : 0u;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ent += (uint32_t)__shfl_xor((int)ent, o);
-        if (lane == 0) s_stat[wave] = make_uint2(ent, st_trips);
-        __syncthreads();
-        if (tid == 0)
-            p.im.tile_stats[(size_t)p.V * p.T + vt] = make_uint4(s_stat[0].x + s_stat[1].x + s_stat[2].x + s_stat[3].x,
-                                                                 s_stat[0].y + s_stat[1].y + s_stat[2].y + s_stat[3].y, 0u, (uint32_t)rounds);
+        const uint2 sum = tile_stat_sums<4>((lane & 15) == 0, st_entries, st_trips, lane, wave, s_stat);
+        if (tid == 0) p.im.tile_stats[(size_t)p.V * p.T + vt] = make_uint4(sum.x, sum.y, 0u, (uint32_t)rounds);
     }
 }
 
@@ -419,7 +339,7 @@ __device__ __forceinline__ v2f sel2(bool a, bool b, v2f t, v2f f) { return v2f{a
 // Per pixel the arithmetic is the reference's, in the reference's order (every operation on a pair is the scalar operation
 // on each half); the masks are applied to one factor (0 x finite) instead of to the nine products, which adds (+-)0 to a sum
 // where the other kernel adds +0.  The order in which a cell's 16 pixels are added differs from the other kernel's.
-// Batches of 256 entries are staged by 128 threads, two entries each (entry e of the batch by thread e & 127).
+// Batches of 256 entries are staged by 128 threads, two entries each (entry e of the batch by thread e & 127): compact_cells<2>.
 template <bool FAST_EXP, bool DET>
 __global__ __launch_bounds__(128) void blend_backward_pair_kernel(BwdParams p) {
     __shared__ uint32_t s_id[256];
@@ -476,59 +396,21 @@ __global__ __launch_bounds__(128) void blend_backward_pair_kernel(BwdParams p) {
     __syncthreads();
     const uint32_t todo = max(s_max[0], s_max[1]);             // <= rg.y - rg.x
     const int rounds = (int)((todo + 255u) / 256u);
-    const bool colors_per_set = p.colors_pre != nullptr;
     uint32_t st_entries = 0, st_trips = 0;
     for (int i = 0; i < rounds; ++i) {
         // batch entry e (0..255) = 1-based list index contributor = todo - (i * 256 + e), staged by thread e & 127
-        unsigned m16[2] = {0u, 0u};
+        unsigned m16[2];
         int idxs[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int e = h * 128 + tid;
-            const int idx = (int)todo - 1 - (i * 256 + e);
-            idxs[h] = idx;
-            if (idx >= 0) {
-                const uint32_t id = p.bn.point_list[rg.x + (uint32_t)idx];
-                const BlendRecord* rec = p.g.blend + vo + id;
-                const float4 co = rec->co;
-                float4 rc = rec->rc;
-                const float2 xy = rec->xy;
-                m16[h] = cell_mask(xy, co, rc.w, tx0, ty0);
-                if (colors_per_set) {
-                    const float* c = p.colors_pre + 3 * ((size_t)s * p.P + id);
-                    rc.x = c[0]; rc.y = c[1]; rc.z = c[2];
-                }
-                s_id[e] = id; s_xy[e] = xy; s_co[e] = co; s_rgbc[e] = rc;
-            } else {
-                s_id[e] = 0u; s_xy[e] = make_float2(0.f, 0.f); s_co[e] = make_float4(0.f, 0.f, 0.f, 0.f); s_rgbc[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+            idxs[h] = (int)todo - 1 - (i * 256 + e);
+            m16[h] = stage_replayed<false>(p, rg.x, idxs[h], e, vo, s, tx0, ty0, s_id, s_xy, s_co, s_rgbc);
         }
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const unsigned long long keep = __ballot((m16[h] >> c) & 1u);
-                if (lane == 0) reinterpret_cast<uint32_t*>(&s_cnt[c])[2 * h + wave] = (uint32_t)__popcll(keep);
-            }
-        __syncthreads();
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const unsigned long long keep = __ballot((m16[h] >> c) & 1u);
-                if ((m16[h] >> c) & 1u) {
-                    const uint4 cn = s_cnt[c];
-                    const int part = 2 * h + wave;                      // which 64 entries of the batch
-                    const uint32_t ahead = (part > 0 ? cn.x : 0u) + (part > 1 ? cn.y : 0u) + (part > 2 ? cn.z : 0u);
-                    s_list[c][ahead + (uint32_t)__popcll(keep & lanes_before)] = (uint8_t)(h * 128 + tid);
-                }
-            }
-        __syncthreads();
         {
-            const uint4 cn = s_cnt[cell];
-            const uint32_t tot = cn.x + cn.y + cn.z + cn.w;
+            const uint32_t tot = compact_cells<2>(m16, cell, tid, lane, wave, lanes_before, s_cnt, s_list);
             const uint32_t first = todo - (uint32_t)(i * 256);
-            struct Entry { float2 xy; float4 co; float4 rc; };
+            using Entry = CellEntry<false>;
             auto load = [&](uint32_t j) { return Entry{s_xy[j], s_co[j], s_rgbc[j]}; };
             auto step = [&](uint32_t k, uint32_t j, const Entry& e) {
                 const float dx = e.xy.x - pfx;
@@ -587,20 +469,9 @@ __global__ __launch_bounds__(128) void blend_backward_pair_kernel(BwdParams p) {
                     }
                 }
             };
-            const uint32_t* lst = reinterpret_cast<const uint32_t*>(s_list[cell]);
-            uint32_t word = lst[0];
-            Entry ea = load(word & 255u), eb;
-            if constexpr (kRasterStats) st_entries += tot;
-            uint32_t k = 0;
-            for (; wave_ballot(k < tot) != 0ull && !(kRasterAblate && (p.ablate & 4)); k += 4) {
-                const uint32_t word_next = lst[(k >> 2) + 1u];
-                eb = load((word >> 8) & 255u);  step(k, word & 255u, ea);
-                ea = load((word >> 16) & 255u); step(k + 1u, (word >> 8) & 255u, eb);
-                eb = load(word >> 24);          step(k + 2u, (word >> 16) & 255u, ea);
-                ea = load(word_next & 255u);    step(k + 3u, word >> 24, eb);
-                word = word_next;
-            }
-            if constexpr (kRasterStats) st_trips += 2u * k;          // a trip issues 128 pixel slots: counted as two of the 64-slot trips
+            const uint32_t k = walk_cell(s_list[cell], load, step,
+                                         [&](uint32_t at) { return wave_ballot(at < tot) != 0ull && !(kRasterAblate && (p.ablate & 4)); });
+            if constexpr (kRasterStats) { st_entries += tot; st_trips += 2u * k; }     // a trip issues 128 pixel slots: counted as two of the 64-slot trips
         }
         __syncthreads();
         if constexpr (!DET) {
@@ -610,53 +481,15 @@ __global__ __launch_bounds__(128) void blend_backward_pair_kernel(BwdParams p) {
             }
         } else {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int e = h * 128 + tid;
-                float c9[9];
-                bool any = false;
-#pragma unroll
-                for (int z = 0; z < 9; ++z) {
-                    const float a0 = s_acc[0][z][e], a1 = s_acc[1][z][e];
-                    c9[z] = a0 + a1;
-                    any = any || a0 != 0.f || a1 != 0.f;           // the copies, not their sum (see blend_backward_kernel)
-                }
-                if (idxs[h] >= 0) {
-                    if (any) {
-#pragma unroll
-                        for (int w = 0; w < NACC; ++w)
-#pragma unroll
-                            for (int z = 0; z < 9; ++z) s_acc[w][z][e] = 0.f;
-                    }
-                    const uint32_t id = s_id[e];
-                    const size_t gv = vo + id;
-                    int x0, y0, x1, y1;
-                    tile_rect(s_xy[e].x, s_xy[e].y, p.radii[gv], p.gx, p.gy, &x0, &y0, &x1, &y1);
-                    const size_t slot = (size_t)p.slot_base[gv] + (size_t)((by - y0) * (x1 - x0) + (bx - x0));
-                    p.slot_a[slot] = make_float4(c9[0], c9[1], c9[2], c9[3]);
-                    p.slot_b[slot] = make_float4(c9[4], c9[5], c9[6], c9[7]);
-                    p.slot_c[slot] = c9[8];
-                }
-            }
+            for (int h = 0; h < 2; ++h) store_slots(p, s_acc, s_id, s_xy, h * 128 + tid, idxs[h] >= 0, vo, bx, by);
         }
     }
     if constexpr (DET) {
-        if (tid == 0) {
-            unsigned long long key = 0ull;
-            if (todo > 0) {
-                const uint32_t id = p.bn.point_list[rg.x + todo - 1u];
-                key = ((unsigned long long)__float_as_uint(p.g.depths[vo + id]) << 32) | id;
-            }
-            p.last_key[vt] = key;
-        }
+        if (tid == 0) write_last_key(p, vt, rg.x, todo, vo);
     }
     if constexpr (kRasterStats) {
-        uint32_t ent = q == 0 ? st_entries : 0u;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ent += (uint32_t)__shfl_xor((int)ent, o);
-        if (lane == 0) s_stat[wave] = make_uint2(ent, st_trips);
-        __syncthreads();
-        if (tid == 0)
-            p.im.tile_stats[(size_t)p.V * p.T + vt] = make_uint4(s_stat[0].x + s_stat[1].x, s_stat[0].y + s_stat[1].y, 0u, (uint32_t)rounds);
+        const uint2 sum = tile_stat_sums<2>(q == 0, st_entries, st_trips, lane, wave, s_stat);
+        if (tid == 0) p.im.tile_stats[(size_t)p.V * p.T + vt] = make_uint4(sum.x, sum.y, 0u, (uint32_t)rounds);
     }
 }
 
@@ -996,29 +829,34 @@ static void launch_blend_backward(const BwdParams& p, int V, hipStream_t st, boo
     const dim3 grid((unsigned)(V * p.T));
     size_t pad = 0;                // tools' library: DGS_RASTER_BWD_LDS_PAD = bytes of unused LDS per workgroup (fewer workgroups per CU)
     if constexpr (kRasterAblate) { static const int e = [] { const char* v = getenv("DGS_RASTER_BWD_LDS_PAD"); return v ? atoi(v) : 0; }(); pad = (size_t)e; }
-    if (aux) {
-        // the aux form lives in the one-pixel walk only, whatever pair_walk or DGS_RASTER_BWD_WALK say (depth and alpha maps)
-        if (p.exact_exp) hipLaunchKernelGGL((blend_backward_kernel<false, DET, true>), grid, dim3(256), pad, st, p);
-        else hipLaunchKernelGGL((blend_backward_kernel<true, DET, true>), grid, dim3(256), pad, st, p);
-    } else if (pair_walk<DET>(V * p.T)) {
-        if (p.exact_exp) hipLaunchKernelGGL((blend_backward_pair_kernel<false, DET>), grid, dim3(128), pad, st, p);
-        else hipLaunchKernelGGL((blend_backward_pair_kernel<true, DET>), grid, dim3(128), pad, st, p);
-    } else {
-        if (p.exact_exp) hipLaunchKernelGGL((blend_backward_kernel<false, DET>), grid, dim3(256), pad, st, p);
-        else hipLaunchKernelGGL((blend_backward_kernel<true, DET>), grid, dim3(256), pad, st, p);
-    }
+    // the aux form lives in the one-pixel walk only, whatever pair_walk or DGS_RASTER_BWD_WALK say (depth and alpha maps)
+    const bool pair = !aux && pair_walk<DET>(V * p.T);
+    with_flag(!p.exact_exp, [&](auto fast) {
+        constexpr bool FAST = decltype(fast)::value;
+        if (pair) hipLaunchKernelGGL((blend_backward_pair_kernel<FAST, DET>), grid, dim3(128), pad, st, p);
+        else with_flag(aux, [&](auto ax) { hipLaunchKernelGGL((blend_backward_kernel<FAST, DET, decltype(ax)::value>), grid, dim3(256), pad, st, p); });
+    });
+}
+
+// the deterministic form's gather: the tiles' keys in LDS when they fit
+static void launch_gather_partials(const BwdParams& p, int V, hipStream_t st, bool aux) {
+    const dim3 grid((unsigned)((p.P + 255) / 256), (unsigned)V);
+    with_flag(p.T <= 4096, [&](auto lds) {
+        with_flag(aux, [&](auto ax) {
+            constexpr bool LDS_KEYS = decltype(lds)::value;
+            hipLaunchKernelGGL((gather_partials_kernel<LDS_KEYS, decltype(ax)::value>), grid, dim3(256), LDS_KEYS ? (size_t)p.T * 8 : 0, st, p);
+        });
+    });
 }
 
 static void launch_preprocess_backward(const BwdParams& p, int S, size_t ns, hipStream_t st, bool aux) {
     const dim3 grid((unsigned)((ns + 255) / 256));
-    if (aux) {
-        if (!p.shs || (p.M == 1 && p.D == 0)) hipLaunchKernelGGL((preprocess_backward_kernel<1, true>), grid, dim3(256), 0, st, p, S);
-        else hipLaunchKernelGGL((preprocess_backward_kernel<16, true>), grid, dim3(256), 0, st, p, S);
-        return;
-    }
     // one coefficient (degree 0, or precomputed colours: no SH at all) / up to 16
-    if (!p.shs || (p.M == 1 && p.D == 0)) hipLaunchKernelGGL(preprocess_backward_kernel<1>, grid, dim3(256), 0, st, p, S);
-    else hipLaunchKernelGGL(preprocess_backward_kernel<16>, grid, dim3(256), 0, st, p, S);
+    with_flag(!p.shs || (p.M == 1 && p.D == 0), [&](auto one) {
+        with_flag(aux, [&](auto ax) {
+            hipLaunchKernelGGL((preprocess_backward_kernel<decltype(one)::value ? 1 : 16, decltype(ax)::value>), grid, dim3(256), 0, st, p, S);
+        });
+    });
 }
 
 }  // namespace dgs
@@ -1075,13 +913,7 @@ extern "C" int dgs_raster_backward(const DgsRasterBackwardArgs* a, dgs_stream_t 
         hipLaunchKernelGGL(order_tiles_kernel, dim3(1), dim3(1024), 0, st, p.im.tile_work, V * p.T, p.im.tile_order);
         launch_blend_backward<true>(p, V, st, aux);
         if (a->debug && hipStreamSynchronize(st) != hipSuccess) return DGS_ERR_DEVICE;
-        const dim3 gridPV((unsigned)((P + 255) / 256), (unsigned)V);
-        if (aux) {
-            if (p.T <= 4096) hipLaunchKernelGGL((gather_partials_kernel<true, true>), gridPV, dim3(256), (size_t)p.T * 8, st, p);
-            else hipLaunchKernelGGL((gather_partials_kernel<false, true>), gridPV, dim3(256), 0, st, p);
-        }
-        else if (p.T <= 4096) hipLaunchKernelGGL((gather_partials_kernel<true>), gridPV, dim3(256), (size_t)p.T * 8, st, p);
-        else hipLaunchKernelGGL((gather_partials_kernel<false>), gridPV, dim3(256), 0, st, p);
+        launch_gather_partials(p, V, st, aux);
         launch_preprocess_backward(p, S, ns, st, aux);
         if (a->debug && hipStreamSynchronize(st) != hipSuccess) return DGS_ERR_DEVICE;
         return hipGetLastError() == hipSuccess ? DGS_OK : DGS_ERR_DEVICE;

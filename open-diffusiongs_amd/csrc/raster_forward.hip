@@ -14,13 +14,14 @@
 //                                                           popcount prefix = sorted tile list, O(len + P/32), no log factor
 //   renderCUDA                forward.cu:261-374       blend_forward_kernel (LDS-staged 48-byte records incl. colour,
 //                                                       per-Gaussian alpha cut-off so dead wave-iterations skip the exp)
+//                                                       on per-cell index lists: raster_cells.h, shared with the backward
 //
 // The final per-tile order is the reference's: (tile, depth bits, Gaussian index) -- a stable sort of the depth
 // keys breaks ties by index exactly like the reference's stable radix over emission order.
 // All V views of a call are processed by the same launches (grid.y / grid.z = view).
 #include <string.h>
 
-#include "raster_common.h"
+#include "raster_cells.h"
 
 namespace dgs {
 
@@ -1151,12 +1152,11 @@ __device__ __forceinline__ void scan_more(const FwdParams& p, TileScan& s, uint3
 // l: cell column l >> 4, pixel (l & 3, (l >> 2) & 3) inside it).  The tile's list is the reference's -- every Gaussian whose
 // ceil(3 sigma_max) square overlaps the tile -- but a pair contributes only inside the ellipse power >= ln(1 / (255 opacity)),
 // and in the trained-like regime (~3,000 entries per tile, ellipses of a few pixels) a cell meets a fifth of its
-// tile's list.  So a batch of 256 entries is staged in LDS; while staging, every thread works out which of the sixteen cells
-// ITS entry can reach (cell_mask: the ellipse's bounding box, inflated -- conservative, so skipping changes no bit); ballots
-// compact the batch into sixteen index lists, front to back; and the four rows of a wave walk their four lists in lockstep,
-// each lane row reading its own entry.  Per (pixel, entry) the arithmetic is the reference's, in the reference's order
-// (forward.cu:332-358); the body has no per-lane branches: one wave-uniform branch leaves when no lane passes the alpha
-// cut-off, everything behind it is selects.
+// tile's list.  So the list goes through the cell-list mechanism of raster_cells.h, front to back: batches of 256 entries staged in
+// LDS, compacted into sixteen per-cell index lists, and the four rows of a wave walk their four lists in lockstep, each lane row
+// reading its own entry.  Per (pixel, entry) the arithmetic is the reference's, in the reference's order (forward.cu:332-358); the
+// body has no per-lane branches: one wave-uniform branch leaves when no lane passes the alpha cut-off, everything behind it is
+// selects.
 //
 // AUX (opt-in: DgsRasterForwardArgs.out_depth / out_alpha): the entry's p_view.z is staged BEHIND its pixel coordinates -- the record's
 // (x, y, z, -) is one 16-byte read, the staged one one ds_read_b128 where the colour-only form has a b64 -- and a step makes one more
@@ -1164,8 +1164,7 @@ __device__ __forceinline__ void scan_more(const FwdParams& p, TileScan& s, uint3
 // final_T needs nothing per step.  The colour-only instantiations are the code they were: no LDS, register or store of this form.
 template <bool SCAN, bool FAST_EXP, bool AUX = false>
 __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
-    using XY = typename std::conditional<AUX, float4, float2>::type;
-    __shared__ XY s_xy[256];
+    __shared__ CellXY<AUX> s_xy[256];
     __shared__ float4 s_co[256];
     __shared__ float4 s_rgbc[256];
     __shared__ uint4 s_cnt[16];                           // [cell] entries of the batch the cell keeps, per staging wave
@@ -1208,55 +1207,20 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
             while (ts.waiting < need && ts.next_rank < (uint32_t)p.P)
                 scan_more(p, ts, s_ring, s_scan, rects, order, p.bn.point_list + rg.x, rg.y - rg.x, (uint32_t)bx, (uint32_t)by, lane, wave, lanes_before);
         }
-        unsigned m16 = 0u;
-        if (pos < rg.y && (!SCAN || (uint32_t)tid < ts.waiting)) {
-            const uint32_t id = SCAN ? s_ring[(ts.head + (uint32_t)tid) & (kRing - 1u)] : p.bn.point_list[pos];
-            const BlendRecord* rec = p.g.blend + vo + id;      // one line per entry (raster_state.h)
-            const float4 co = rec->co;
-            const float4 rc = rec->rc;
-            XY xy;
-            if constexpr (AUX) xy = *reinterpret_cast<const float4*>(&rec->xy);     // (x, y, z, -)
-            else xy = rec->xy;
-            s_xy[tid] = xy; s_co[tid] = co; s_rgbc[tid] = rc;
-            m16 = cell_mask(make_float2(xy.x, xy.y), co, rc.w, tx0, ty0);
-        } else {
-            // a slot without an entry holds a finite record: the walk reads ahead of its lists (stale indices), and the product-default
-            // arithmetic multiplies a masked-out lane's colour by a zero weight instead of selecting -- 0 * NaN from LDS left by an
-            // earlier kernel would poison the pixel
-            if constexpr (AUX) s_xy[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-            else s_xy[tid] = make_float2(0.f, 0.f);
-            s_co[tid] = make_float4(0.f, 0.f, 0.f, 0.f); s_rgbc[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        unsigned long long keeps[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            keeps[c] = __ballot((m16 >> c) & 1u);
-            if (lane == 0) reinterpret_cast<uint32_t*>(&s_cnt[c])[wave] = (uint32_t)__popcll(keeps[c]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            if ((m16 >> c) & 1u) {
-                const uint4 cn = s_cnt[c];
-                const uint32_t ahead = (wave > 0 ? cn.x : 0u) + (wave > 1 ? cn.y : 0u) + (wave > 2 ? cn.z : 0u);
-                s_list[c][ahead + (uint32_t)__popcll(keeps[c] & lanes_before)] = (uint8_t)tid;
-            }
-        }
-        __syncthreads();
+        const bool has = pos < rg.y && (!SCAN || (uint32_t)tid < ts.waiting);
+        uint32_t id = 0u;
+        if (has) id = SCAN ? s_ring[(ts.head + (uint32_t)tid) & (kRing - 1u)] : p.bn.point_list[pos];
+        const unsigned m16[1] = {stage_entry<AUX>(has, p.g.blend + vo, nullptr, id, tid, tx0, ty0, s_xy, s_co, s_rgbc)};
+        const uint32_t kept = compact_cells<1>(m16, cell, tid, lane, wave, lanes_before, s_cnt, s_list);
         if (SCAN) { const uint32_t took = min(need, ts.waiting); ts.head += took; ts.waiting -= took; }
         const uint32_t base = (uint32_t)i * 256u;
         const unsigned long long alive = __ballot(!done);
         if (alive != 0ull) {                                    // a wave whose 64 pixels are all finished only keeps the barriers
-            const uint4 cn = s_cnt[cell];
-            const uint32_t tot = (((alive >> (16 * row)) & 0xFFFFull) != 0ull) ? cn.x + cn.y + cn.z + cn.w : 0u;
+            const uint32_t tot = (((alive >> (16 * row)) & 0xFFFFull) != 0ull) ? kept : 0u;
             // a lane's OWN list length: 0 once its pixel is finished, so "still walking" is the index compare the step makes anyway
             // (a `done` flag tested per step is a VGPR 0/1 and costs three VALU per step to test and keep)
             uint32_t tot_l = done ? 0u : tot;
-            // software pipeline: the cell's indices arrive four at a time (one 32-bit word, the next word a group ahead), the
-            // entry itself one step ahead, in two register sets that take turns -- the loop is unrolled by the word, so there is
-            // no copy between steps and every shift is a literal (the rotating form spent 13 of its ~45 VALU per step on moves)
-            // (bytes behind `tot` are stale indices of earlier batches: any of them addresses a staged record, none is used)
-            struct Entry { XY xy; float4 co; float4 rc; };
+            using Entry = CellEntry<AUX>;
             auto load = [&](uint32_t j) { return Entry{s_xy[j], s_co[j], s_rgbc[j]}; };
             auto step = [&](uint32_t k, uint32_t j, const Entry& e) {
                 const float dx = e.xy.x - pfx, dy = e.xy.y - pfy;
@@ -1287,18 +1251,7 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
                     last_contributor = blends ? base + j + 1u : last_contributor;
                 }
             };
-            const uint32_t* lst = reinterpret_cast<const uint32_t*>(s_list[cell]);
-            uint32_t word = lst[0];
-            Entry ea = load(word & 255u), eb;
-            uint32_t k = 0;
-            for (; wave_ballot(k < tot_l) != 0ull; k += 4) {
-                const uint32_t word_next = lst[(k >> 2) + 1u];
-                eb = load((word >> 8) & 255u);  step(k, word & 255u, ea);
-                ea = load((word >> 16) & 255u); step(k + 1u, (word >> 8) & 255u, eb);
-                eb = load(word >> 24);          step(k + 2u, (word >> 16) & 255u, ea);
-                ea = load(word_next & 255u);    step(k + 3u, word >> 24, eb);
-                word = word_next;
-            }
+            const uint32_t k = walk_cell(s_list[cell], load, step, [&](uint32_t at) { return wave_ballot(at < tot_l) != 0ull; });
             done = done | (tot_l != tot);                       // finished in this batch (tot >= 1 then), or before it
             if constexpr (kRasterStats) { st_entries += min(tot, k); st_trips += k; }    // the walk leaves a batch once the wave's 64 pixels are finished
         }
@@ -1324,21 +1277,15 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(FwdParams p) {
     uint32_t walked = last_contributor;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) walked = max(walked, (uint32_t)__shfl_xor((int)walked, o));
-    if constexpr (kRasterStats) {
-        uint32_t ent = (lane & 15) == 0 ? st_entries : 0u;             // one lane per 16-lane row: the row's cell
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ent += (uint32_t)__shfl_xor((int)ent, o);
-        if (lane == 0) s_stat[wave] = make_uint2(ent, st_trips);
-    }
+    uint2 stat = make_uint2(0u, 0u);
+    if constexpr (kRasterStats) stat = tile_stat_sums<4>((lane & 15) == 0, st_entries, st_trips, lane, wave, s_stat);   // one lane per 16-lane row: the row's cell
     if (lane == 0) s_walk[wave] = walked;
     __syncthreads();
     if (tid == 0) {
         p.im.tile_work[vt] = max(max(s_walk[0], s_walk[1]), max(s_walk[2], s_walk[3]));
         p.im.tile_cursor[vt] = SCAN ? ts.found : rg.y - rg.x;          // entries of the tile's list that exist in point_list
         p.im.tile_scanned[vt] = SCAN ? ts.next_rank : 0u;              // depth ranks the tile tested (scan form)
-        if constexpr (kRasterStats)
-            p.im.tile_stats[vt] = make_uint4(s_stat[0].x + s_stat[1].x + s_stat[2].x + s_stat[3].x, s_stat[0].y + s_stat[1].y + s_stat[2].y + s_stat[3].y,
-                                             SCAN ? ts.next_rank : 0u, st_batches);
+        if constexpr (kRasterStats) p.im.tile_stats[vt] = make_uint4(stat.x, stat.y, SCAN ? ts.next_rank : 0u, st_batches);
     }
 }
 
@@ -1361,6 +1308,16 @@ __global__ void mark_visible_kernel(int P, const float* means, const float* vm, 
     const float mx = means[3 * i], my = means[3 * i + 1], mz = means[3 * i + 2];
     const float tz = vm[2] * mx + vm[6] * my + vm[10] * mz + vm[14];
     present[i] = !(tz <= 0.2f);   // in_frustum, auxiliary.h:154
+}
+
+// the blend of one binning family (SCAN: the lists are found while blending) in the call's form
+template <bool SCAN>
+static void launch_blend_forward(const FwdParams& p, bool aux, int VT, size_t lds_pad, hipStream_t st) {
+    with_flag(!p.exact_exp, [&](auto fast) {
+        with_flag(aux, [&](auto ax) {
+            hipLaunchKernelGGL((blend_forward_kernel<SCAN, decltype(fast)::value, decltype(ax)::value>), dim3(VT), dim3(256), lds_pad, st, p);
+        });
+    });
 }
 
 static int check(hipStream_t st, int debug) {
@@ -1563,12 +1520,7 @@ int dgs_raster_forward(DgsRasterForwardArgs* a, dgs_stream_t stream) {
     if ((forms & ((1 << kFormRankSort) | (1 << kFormScan))) && !radix_done) radix_sort();
     if (forms & (1 << kFormScan)) {
         hipLaunchKernelGGL(rank_rects_kernel, gridP, dim3(256), 0, st, p);
-        if (aux) {
-            if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<true, false, true>), dim3(VT), dim3(256), blend_pad, st, p);
-            else hipLaunchKernelGGL((blend_forward_kernel<true, true, true>), dim3(VT), dim3(256), blend_pad, st, p);
-        }
-        else if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<true, false>), dim3(VT), dim3(256), blend_pad, st, p);
-        else hipLaunchKernelGGL((blend_forward_kernel<true, true>), dim3(VT), dim3(256), blend_pad, st, p);
+        launch_blend_forward<true>(p, aux, VT, blend_pad, st);
     }
     if (forms & ((1 << kFormRankSort) | (1 << kFormBitonic))) {
         if (lds_tiles) hipLaunchKernelGGL((emit_instances_kernel<true>), gridP, dim3(256), (size_t)p.T * 8, st, p);
@@ -1588,14 +1540,7 @@ int dgs_raster_forward(DgsRasterForwardArgs* a, dgs_stream_t stream) {
         else if (p.bitonic_cap >= 4096 && nt_env != 256) hipLaunchKernelGGL(tile_bitonic_kernel<512>, dim3(VT), dim3(512), lds, st, p);
         else hipLaunchKernelGGL(tile_bitonic_kernel<256>, dim3(VT), dim3(256), lds, st, p);
     }
-    if (forms & ((1 << kFormRankSort) | (1 << kFormBitonic))) {
-        if (aux) {
-            if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<false, false, true>), dim3(VT), dim3(256), blend_pad, st, p);
-            else hipLaunchKernelGGL((blend_forward_kernel<false, true, true>), dim3(VT), dim3(256), blend_pad, st, p);
-        }
-        else if (p.exact_exp) hipLaunchKernelGGL((blend_forward_kernel<false, false>), dim3(VT), dim3(256), blend_pad, st, p);
-        else hipLaunchKernelGGL((blend_forward_kernel<false, true>), dim3(VT), dim3(256), blend_pad, st, p);
-    }
+    if (forms & ((1 << kFormRankSort) | (1 << kFormBitonic))) launch_blend_forward<false>(p, aux, VT, blend_pad, st);
     return check(st, a->debug);
 }
 

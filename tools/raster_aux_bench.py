@@ -1,6 +1,7 @@
 """What the rasterizer's depth / alpha maps cost (forward_views(aux=True), backward_views(grad_depth=, grad_alpha=)) against the
 workaround they replace -- a second render of the same Gaussians with colors_precomp = (z, 1, 0) on background 0, one set per view --
-and what the default (colour-only) call costs against another build of the library (the parent commit's), both loaded side by side.
+and what the default (colour-only) call costs against another build of the library (the parent commit's), both loaded side by side
+(with --base also: are the default colour and the deterministic form's gradients the base build's, bit for bit).
     python tools/raster_aux_bench.py [--base <other libdgs_hip.so>] [--pairs 20] [--out profiles/raster_aux_bench.json]
 Every comparison alternates its two sides inside one process, a pair at a time, each side between device events; an A/A series (the
 base build against itself, or the product build when no base is given) measures the spread of such pairs on the box.  The structural
@@ -142,6 +143,16 @@ def main():
         if base is not None:
             col_new, col_base = s.fwd(new, cap)[1], s.fwd(base, cap)[1]
             row["default colour bit-identical with base"] = bool(torch.equal(col_new, col_base))
+
+            def det_grads(be, **kw):            # the deterministic backward is reproducible: the two builds must agree bit for bit
+                be.deterministic = True
+                g = s.bwd(be, s.fwd(be, cap, aux=bool(kw)), **kw)
+                det, be.deterministic = be.last_backward_deterministic, False
+                return g if det else {}
+
+            for what, kw in (("", {}), (" with the maps", dict(grad_depth=s.gD, grad_alpha=s.gA))):
+                gn, gb = det_grads(new, **kw), det_grads(base, **kw)
+                row[f"deterministic gradients{what} bit-identical with base"] = bool(gn) and all(torch.equal(gn[k], gb[k]) for k in gn if gn[k] is not None)
             for what, fa, fb, aa in (("forward", f_col, f_ref, "A/A forward: base vs base"),
                                      ("forward + backward", fb_col, fb_ref, "A/A forward + backward: base vs base")):
                 st_ = stats(*pairs(fa, fb, a.pairs))
