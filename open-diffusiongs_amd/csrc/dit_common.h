@@ -128,9 +128,11 @@ __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float c) {
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2_t, a), __builtin_bit_cast(bf2_t, b), c, false);
 #endif
 }
-__device__ __forceinline__ float dot8_bf16(uint4 a, uint4 b) {
-    return dot2_bf16(a.w, b.w, dot2_bf16(a.z, b.z, dot2_bf16(a.y, b.y, dot2_bf16(a.x, b.x, 0.f))));
+// acc + the dot product of 8 bf16 pairs held in two 16-byte registers: four chained v_dot2c_f32_bf16
+__device__ __forceinline__ float dot8_bf16(uint4 a, uint4 b, float acc) {
+    return dot2_bf16(a.w, b.w, dot2_bf16(a.z, b.z, dot2_bf16(a.y, b.y, dot2_bf16(a.x, b.x, acc))));
 }
+__device__ __forceinline__ float dot8_bf16(uint4 a, uint4 b) { return dot8_bf16(a, b, 0.f); }
 
 // compile-time loops: static_for<0, N>([&](auto ic) { constexpr int I = decltype(ic)::value; ... })
 template <int I> struct IC { static constexpr int value = I; };

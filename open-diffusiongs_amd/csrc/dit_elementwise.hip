@@ -85,16 +85,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnParams p) {
 // ring's first slabs, and the workgroups that carry one enter their loop 3 us late and end the launch (profiles/r05_gemm_timeline.txt).
 // Here the same items are the FIRST workgroups of the LayerNorm launch, which is one memory round trip long anyway: an item
 // normalises the sample's live rows itself (the rows' LayerNorm output does not exist yet in this launch: same ln_row, same bits),
-// and then is the GEMM's item with 4 waves instead of 8: K ranges of 512 per wave, the ranges summed in the same order -- the
-// outputs are bit-identical to the GEMM's own items (tests/test_dit_kernels_emu.py, tests/test_dit_gpu.py).
-struct TailEpi {               // what tail_prefetch / tail_store read of a GEMM's parameter block (dit_gemm_epilogue.h)
-    const float *bias, *resid, *gate;
-    void *out, *aux;
-    bf16_t* vt;
-    int N, ldo, gate_stride, rows_per_batch;
-    float q_scale;
-};
-
+// and then is the GEMM's item with 4 waves instead of 8: K ranges of 512 per wave, the ranges summed in the same order, through the
+// item code the GEMM's own side jobs run (dit_gemm_epilogue.h) -- the outputs are bit-identical to theirs
+// (tests/test_dit_kernels_emu.py, tests/test_dit_gpu.py).
 template <int VPL, int EPI>
 __global__ __launch_bounds__(256) void layernorm_rows_gemv_kernel(LnParams p, LnRowsGemv j) {
     constexpr int K = 256 * VPL, KS = K / 512 < 4 ? K / 512 : 4, CS = 4 / KS, CPI = 8 * CS, KW = K / KS;
@@ -108,16 +101,11 @@ __global__ __launch_bounds__(256) void layernorm_rows_gemv_kernel(LnParams p, Ln
         return;
     }
     const int blk = blockIdx.x, kq = wave % KS, cq = wave / KS, k_lo = kq * KW;
-    uint4 w[8];
-    const bf16_t* w_col0 = j.W + (size_t)(blk * CPI + cq * 8) * j.ldw + k_lo + lane * 8;
+    uint4 a[2][1], w[8][1];
+    const bf16_t* w_col0 = j.g.W + (size_t)(blk * CPI + cq * 8) * j.g.ldw + k_lo + lane * 8;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) w[c] = *reinterpret_cast<const uint4*>(w_col0 + (size_t)c * j.ldw);
-    TailEpi te{j.bias, nullptr, nullptr, j.out, j.aux, j.vt, j.N, j.ldo, 0, p.rows_per_batch, j.q_scale};
-    const int er = tid / CPI, ec = tid - er * CPI;                        // the element thread `tid` finishes (tid < 2 CPI)
-    const int erow = b * p.rows_per_batch + j.row0 + er;
-    const bool finisher = tid < 2 * CPI && er < j.nrows;
-    TailOperands ops{0.f, 0.f, 0.f};
-    if (finisher) ops = tail_prefetch<EPI>(te, erow, blk * CPI + ec);
+    for (int c = 0; c < 8; ++c) w[c][0] = *reinterpret_cast<const uint4*>(w_col0 + (size_t)c * j.g.ldw);
+    const Gemv2Element<EPI> e(j.g, tid, CPI, b * p.rows_per_batch + j.row0, blk * CPI, j.nrows);
     if (wave < 2) {
         if (wave < j.nrows) {
             float4 y[VPL];
@@ -130,19 +118,15 @@ __global__ __launch_bounds__(256) void layernorm_rows_gemv_kernel(LnParams p, Ln
         }
     }
     __syncthreads();
-    const uint4 a0 = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(s_rows[0]) + k_lo + lane * 8);
-    const uint4 a1 = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(s_rows[1]) + k_lo + lane * 8);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        float s0 = dot8_bf16(a0, w[c], 0.f), s1 = dot8_bf16(a1, w[c], 0.f);
-        s0 = wave_sum_lane63(s0); s1 = wave_sum_lane63(s1);
-        if (lane == 63) { s_part[(kq * 2 + 0) * CPI + cq * 8 + c] = s0; s_part[(kq * 2 + 1) * CPI + cq * 8 + c] = s1; }
-    }
+    // the A rows come from LDS, through the array itself (an LDS pointer handed to a function would make these flat loads)
+    a[0][0] = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(s_rows[0]) + k_lo + lane * 8);
+    a[1][0] = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(s_rows[1]) + k_lo + lane * 8);
+    gemv2_partials<1>(a, w, s_part, kq, CPI, cq * 8, lane);
     __syncthreads();
-    if (finisher) {
+    if (e.on) {
         float v = 0.f;
-        for (int q = 0; q < KS; ++q) v += s_part[(q * 2 + er) * CPI + ec];
-        tail_store<EPI>(te, erow, blk * CPI + ec, v, ops);
+        for (int q = 0; q < KS; ++q) v += e.partial(s_part, q);
+        e.store(j.g, v);
     }
 }
 
@@ -390,9 +374,8 @@ int launch_layernorm_rows_gemv(const DgsDitLayerNormArgs* a, const DgsDitGemmArg
     p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : a->rows;
     p.out_f32 = 0; p.eps = a->eps; p.x = a->x; p.weight = nullptr; p.shift = a->shift; p.scale = a->scale; p.out = a->out;
     LnRowsGemv j;
-    j.W = g->W; j.bias = g->bias; j.out = g->out; j.aux = g->aux; j.vt = g->vt; j.N = g->N; j.ldw = g->ldw; j.ldo = g->ldo; j.epilogue = g->epilogue;
+    j.g = gemm_core(g);
     j.nrows = g->valid_rows - (g->valid_rows - 1) / 256 * 256; j.row0 = g->valid_rows - j.nrows;
-    j.q_scale = g->q_scale != 0.0f ? g->q_scale : 1.0f;
     const int ks = a->width / 512 < 4 ? a->width / 512 : 4, cpi = 8 * (4 / ks);
     j.items = g->N / cpi;
     const dim3 grid(j.items + (p.rows_per_batch + 3) / 4, (a->rows + p.rows_per_batch - 1) / p.rows_per_batch), block(256);

@@ -23,36 +23,13 @@ namespace dgs {
 constexpr int BM = 128, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;   // 16 KiB: A tile of one stage (the W tile is BN/128 of that)
 
-struct GemmParams {
-    int M, N, K, lda, ldw, ldo, gate_stride, rows_per_batch, valid_rows, tiles_n, ntiles, tiles_m, map_mode;
+struct GemmParams : GemmCore {
+    int tiles_n, ntiles, tiles_m, map_mode;
     int rows_ps, full_rows;          // per sample: 128-row tile rows, and how many of them hold a live 32-row block (a prefix)
-    int ntail, tail_row0;            // GEMV items (one 32-column block of one sample each) for a last tile row with <= 2 live rows,
-                                     // taken by the first `ntail` workgroups; tail_row0 = that row's first token (row in sample)
+    int ntail, tail_row0;            // GEMV items (8 output columns of one sample each) for a last tile row with <= 2 live rows, BEHIND
+                                     // the `ntiles` tile workgroups in the grid; tail_row0 = that row's first token (row in sample)
     int k_per_batch;                 // reduction elements per sample (K when the reduction dimension is not batched)
-    long long a_batch_stride, w_batch_stride;   // element stride between samples along the reduction (weight-gradient GEMMs)
-    const bf16_t* A;
-    const bf16_t* W;
-    const float* bias;
-    void* out;
-    const float* gate;
-    const float* resid;              // GATE_RESIDUAL input stream (== out for the in-place inference form)
-    bf16_t* vt;                      // transposed bf16 copy [batch, N, rows_per_batch] (QKV: V only)
-    void* aux;                       // GELU: u out; GATE_RESIDUAL: y out; DGELU: u in   (bf16 [M, ldo])
-    float q_scale;                   // QKV: factor on the q features
 };
-
-__device__ __forceinline__ float gelu_tanh(float x) {
-    // nn.GELU(approximate="tanh"): 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) == x * sigmoid(2u)
-    const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-    return x / (1.0f + __expf(-2.0f * u));
-}
-
-// d/dx of gelu_tanh: with s = sigmoid(2u), u = c (x + a x^3):  s + x s (1 - s) 2 c (1 + 3 a x^2)
-__device__ __forceinline__ float dgelu_tanh(float x) {
-    const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-    const float sg = 1.0f / (1.0f + __expf(-2.0f * u));
-    return sg + x * sg * (1.0f - sg) * (2.0f * 0.7978845608028654f) * (1.0f + 3.0f * 0.044715f * x * x);
-}
 
 // Stage one [ROWS][64] bf16 tile: ROWS/8 wave-instructions of 1 KiB (8 rows each); wave w issues pieces (ROWS/32) w ...
 template <int ROWS>
@@ -137,22 +114,19 @@ __device__ __forceinline__ void main_loop(const GemmParams& p, char* lds, int m0
 // three tiles, +10 us.)  While the chip
 // streams GEMM tiles an L2 round trip costs microseconds, so an item is ONE trip: the four waves split K, every wave
 // issues all of its loads (8 columns x its K quarter, 16 bytes per lane) before the first v_dot2c_f32_bf16; the partial
-// sums meet in LDS and 16 lanes apply the epilogue element-wise (same arithmetic as store_strip).
+// sums meet in LDS and 16 lanes apply the epilogue element-wise (the shared item code of dit_gemm_epilogue.h).
 template <int EPI>
 __device__ __forceinline__ void gemv_tail_rows(const GemmParams& p, char* lds, int item, int wave, int lane) {
     constexpr int CPI = 8;                                   // columns per item
     const int nblk = p.N / CPI, b = item / nblk, tn0 = (item - b * nblk) * CPI;
     const int tm0 = b * p.rows_per_batch + p.tail_row0;
-    const int kw = p.K / 4, k_lo = wave * kw;                // this wave's K quarter (K % 512 == 0: a multiple of 128)
-    const int nch = (kw + 511) / 512;                        // 512-element chunks (64 lanes x 8), at most 2 (K <= 4096)
+    const int kw = p.K / 4, k_lo = wave * kw;                // this wave's K quarter (K % 512 == 0, K <= 4096: at most two 512-element chunks)
+    const Gemv2Element<EPI> e(p, wave * 64 + lane, CPI, tm0, tn0, p.valid_rows - p.tail_row0);
+    const int nch = (kw + 511) / 512;                        // 512-element chunks (64 lanes x 8), at most 2
     const bool on0 = lane * 8 < kw, on1 = 512 + lane * 8 < kw;
     const bf16_t* a_row0 = p.A + (size_t)tm0 * p.lda + k_lo + lane * 8;
     const bf16_t* w_col0 = p.W + (size_t)tn0 * p.ldw + k_lo + lane * 8;
     const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
-    const int er = lane / CPI, ec = lane - er * CPI;         // the element lane `lane` of wave 0 finishes (lanes 0 .. 2 CPI - 1)
-    const bool finisher = wave == 0 && lane < 2 * CPI && p.tail_row0 + er < p.valid_rows;
-    TailOperands ops{0.f, 0.f, 0.f};
-    if (finisher) ops = tail_prefetch<EPI>(p, tm0 + er, tn0 + ec);
     uint4 a[2][2], w[CPI][2];
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) {
@@ -163,19 +137,9 @@ __device__ __forceinline__ void gemv_tail_rows(const GemmParams& p, char* lds, i
         for (int c = 0; c < CPI; ++c) w[c][ch] = on ? *reinterpret_cast<const uint4*>(w_col0 + (size_t)c * p.ldw + ch * 512) : zero;
     }
     float* const part = reinterpret_cast<float*>(lds);       // [wave][row][column]
-#pragma unroll
-    for (int c = 0; c < CPI; ++c) {
-        float s0 = dot8_bf16(a[0][0], w[c][0], 0.f), s1 = dot8_bf16(a[1][0], w[c][0], 0.f);
-        s0 = dot8_bf16(a[0][1], w[c][1], s0); s1 = dot8_bf16(a[1][1], w[c][1], s1);
-        s0 = wave_sum_lane63(s0); s1 = wave_sum_lane63(s1);
-        if (lane == 63) { part[(wave * 2 + 0) * CPI + c] = s0; part[(wave * 2 + 1) * CPI + c] = s1; }
-    }
+    gemv2_partials<2>(a, w, part, wave, CPI, 0, lane);
     __syncthreads();
-    if (finisher) {
-        const int r = er, c = ec;
-        const float v = (part[(0 * 2 + r) * CPI + c] + part[(1 * 2 + r) * CPI + c]) + (part[(2 * 2 + r) * CPI + c] + part[(3 * 2 + r) * CPI + c]);
-        tail_store<EPI>(p, tm0 + r, tn0 + c, v, ops);
-    }
+    if (e.on) e.store(p, (e.partial(part, 0) + e.partial(part, 1)) + (e.partial(part, 2) + e.partial(part, 3)));
 }
 
 // BN = 128: waves 2(M) x 2(N), each 64 x 64 (2 x 2 accumulators).  BN = 64 (used when N / 128 tiles would not fill the
@@ -240,89 +204,28 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmParams p) {
         else if (live0) main_loop<BN, NI, 1, false>(p, lds, m0, n0, wave, lane, wm, wn, acc);
         else main_loop<BN, NI, 0, false>(p, lds, m0, n0, wave, lane, wm, wn, acc);
     }
-    const int fhalf = lane >> 5;
-
-    // ---- epilogue, staged through LDS (dit_gemm_epilogue.h) for everything the inference sequence launches; the stages are
-    //      idle (main_loop ends with a barrier), every wave takes a private patch ----
-    if (epi_staged<EPI>(p)) {
-        char* patch = lds + wave * epi_strip_bytes(NI);
-        if constexpr (EPI == DGS_EPI_GATE_RESIDUAL) {
-            // both strips' residual values in ONE round trip: out may alias resid, so the second strip's loads cannot move above
-            // the first strip's stores by themselves
-            float4 pre[2][4 * NI];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-                if (mi == 0 ? live0 : live1) residual_prefetch<NI>(p, m0 + wm * 64 + mi * 32, n0 + wn * (BN / 2), lane, pre[mi]);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-                if (mi == 0 ? live0 : live1) store_strip<EPI, NI>(p, acc[mi], m0 + wm * 64 + mi * 32, n0 + wn * (BN / 2), lane, patch, pre[mi]);
-            return;
-        }
+    // ---- epilogue, staged through LDS (dit_gemm_epilogue.h); the stages are idle (main_loop ends with a barrier), every wave
+    //      takes a private patch ----
+    char* patch = lds + wave * epi_strip_bytes(NI);
+    if constexpr (EPI == DGS_EPI_GATE_RESIDUAL) {
+        // both strips' residual values in ONE round trip: out may alias resid, so the second strip's loads cannot move above
+        // the first strip's stores by themselves
+        float4 pre[2][4 * NI];
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
-            if (mi == 0 ? live0 : live1) store_strip<EPI, NI>(p, acc[mi], m0 + wm * 64 + mi * 32, n0 + wn * (BN / 2), lane, patch);
+            if (mi == 0 ? live0 : live1) residual_prefetch<NI>(p, m0 + wm * 64 + mi * 32, n0 + wn * (BN / 2), lane, pre[mi]);
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+            if (mi == 0 ? live0 : live1) store_strip<EPI, NI>(p, acc[mi], m0 + wm * 64 + mi * 32, n0 + wn * (BN / 2), lane, patch, pre[mi]);
         return;
     }
-
-    // ---- epilogue (training variants).  D fragment: col (n) = lane & 31, row (m) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5): a lane holds, for ONE
-    //      output feature, four groups of four consecutive rows -> row-major stores are 2/4-byte per row, the optional
-    //      transposed copy ([batch, N, rows_per_batch], wanted by the attention and weight-gradient kernels) is one 8-byte
-    //      store per group.
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-        const int n = n0 + wn * (BN / 2) + ni * 32 + (lane & 31);
-        const float bias = p.bias ? p.bias[n] : 0.0f;
-        const float qs = (EPI == DGS_EPI_QKV && n < p.N / 3) ? p.q_scale : 1.0f;      // pre-scaled queries
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-            if (!(mi == 0 ? live0 : live1)) continue;
-            const int mbase = m0 + wm * 64 + mi * 32 + 4 * fhalf;
-            const int b = mbase / p.rows_per_batch;          // a 32-row block never straddles samples (rows_per_batch % 128 == 0)
-            const bool qkv_v = EPI == DGS_EPI_QKV && n >= (p.N / 3) * 2;
-            bf16_t* tdst = nullptr;                           // transposed destination of this lane's feature
-            if (EPI == DGS_EPI_QKV) {
-                if (qkv_v) tdst = p.vt + ((size_t)b * (p.N / 3) + (n - (p.N / 3) * 2)) * p.rows_per_batch + (mbase - b * p.rows_per_batch);
-            } else if ((EPI == DGS_EPI_BF16 || EPI == DGS_EPI_GELU_BF16 || EPI == DGS_EPI_DGELU_BF16) && p.vt) {
-                tdst = p.vt + ((size_t)b * p.N + n) * p.rows_per_batch + (mbase - b * p.rows_per_batch);
-            }
-            float gate = 0.0f;
-            if (EPI == DGS_EPI_GATE_RESIDUAL) gate = p.gate[(size_t)b * p.gate_stride + n];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float o4[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int m = mbase + q + 8 * g;
-                    const float v = EPI == DGS_EPI_QKV ? (acc[mi][ni][4 * g + q] + bias) * qs : acc[mi][ni][4 * g + q] + bias;
-                    const size_t o = (size_t)m * p.ldo + n;
-                    if (EPI == DGS_EPI_BF16) {
-                        o4[q] = v;
-                        reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(v);
-                    } else if (EPI == DGS_EPI_QKV) {
-                        o4[q] = v;
-                        if (!qkv_v) reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(v);
-                    } else if (EPI == DGS_EPI_GELU_BF16) {
-                        o4[q] = gelu_tanh(v);
-                        reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(o4[q]);
-                        if (p.aux) reinterpret_cast<bf16_t*>(p.aux)[o] = (bf16_t)f2bf_fast(v);
-                    } else if (EPI == DGS_EPI_DGELU_BF16) {
-                        o4[q] = v * dgelu_tanh(bf2f(reinterpret_cast<const bf16_t*>(p.aux)[o]));
-                        reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(o4[q]);
-                    } else if (EPI == DGS_EPI_GATE_RESIDUAL) {
-                        reinterpret_cast<float*>(p.out)[o] = p.resid[o] + gate * v;
-                        if (p.aux) reinterpret_cast<bf16_t*>(p.aux)[o] = (bf16_t)f2bf_fast(v);
-                    } else {
-                        reinterpret_cast<float*>(p.out)[o] = v;
-                    }
-                }
-                if (tdst) *reinterpret_cast<uint2*>(tdst + 8 * g) = make_uint2(pack_bf2(o4[0], o4[1]), pack_bf2(o4[2], o4[3]));
-            }
-        }
-    }
+    for (int mi = 0; mi < 2; ++mi)
+        if (mi == 0 ? live0 : live1) store_strip<EPI, NI>(p, acc[mi], m0 + wm * 64 + mi * 32, n0 + wn * (BN / 2), lane, patch);
 }
 
 int sliced_gemm_tile(int M, int N, int K, int epilogue, int k_per_batch, int rows_per_batch, int valid_rows);   // dit_gemm_deep.hip
-int launch_sliced_gemm(const DgsDitGemmArgs* a, int bn, int rows_per_batch, int valid_rows, hipStream_t st, bool quad, bool rows_external);
+int launch_sliced_gemm(const GemmCore& c, int epilogue, int bn, hipStream_t st, bool quad, bool rows_external);
 bool sliced_rows_are_gemv(int K, int N, int valid_rows);
 bool sliced128_eligible(int M, int N, int K, int epilogue, int k_per_batch, int rows_per_batch);
 int splitk_plan(int M, int N, int K, int k_per_batch, int* splits_per_batch);
@@ -333,12 +236,14 @@ int launch_splitk_gemm(const DgsDitGemmArgs* a, int k_per_batch, hipStream_t st)
 using namespace dgs;
 
 template <int EPI>
-static void launch_gemm(const GemmParams& p0, int bn, hipStream_t st) {
-    GemmParams p = p0;
+static void launch_gemm(const GemmCore& c, int k_per_batch, int bn, hipStream_t st) {
+    GemmParams p;
+    static_cast<GemmCore&>(p) = c;
+    p.k_per_batch = k_per_batch;
     p.tiles_n = p.N / bn;
     p.rows_ps = p.rows_per_batch / BM;
     p.full_rows = (p.valid_rows + BM - 1) / BM;               // valid rows are a prefix of every sample
-    // a last tile row with one or two live rows is not a tile row: its 32-column blocks are GEMV items (gemv_tail_rows)
+    // a last tile row with one or two live rows is not a tile row: its 8-column blocks are GEMV items (gemv_tail_rows)
     const int last_live = p.valid_rows - (p.full_rows - 1) * BM;
     static const int no_tail = getenv("DGS_GEMM_NO_GEMV_TAIL") ? atoi(getenv("DGS_GEMM_NO_GEMV_TAIL")) : 0;   // measurement aid
     p.ntail = 0; p.tail_row0 = 0;
@@ -369,14 +274,7 @@ static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode)
     if (a->epilogue == DGS_EPI_DGELU_BF16 && !a->aux) return DGS_ERR_INVALID_ARGUMENT;
     if ((a->vt || a->epilogue == DGS_EPI_QKV) && a->rows_per_batch <= 0) return DGS_ERR_INVALID_ARGUMENT;
     if (a->rows_per_batch > 0 && (a->rows_per_batch % BM || a->M % a->rows_per_batch)) return DGS_ERR_INVALID_ARGUMENT;
-    GemmParams p;
-    p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldw = a->ldw; p.ldo = a->ldo;
-    p.gate_stride = a->gate_stride; p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : a->M;
-    p.valid_rows = (a->valid_rows > 0 && a->valid_rows < p.rows_per_batch) ? a->valid_rows : p.rows_per_batch;
-    p.k_per_batch = kpb; p.a_batch_stride = a->a_batch_stride; p.w_batch_stride = a->w_batch_stride;
-    p.A = a->A; p.W = a->W; p.bias = a->bias; p.out = a->out; p.gate = a->gate; p.vt = a->vt; p.aux = a->aux;
-    p.q_scale = a->q_scale != 0.0f ? a->q_scale : 1.0f;
-    p.resid = a->resid ? a->resid : static_cast<const float*>(a->out);
+    const GemmCore p = gemm_core(a);
     hipStream_t st0 = static_cast<hipStream_t>(stream);
     // Kernel choice.  The default is the 128-wide two-stage kernel below; the sliced 256-row kernel (dit_gemm_deep.hip) takes over
     // where its tile count fits the chip (see AUTO).
@@ -399,7 +297,7 @@ static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode)
         const int sbn = sliced_gemm_tile(a->M, a->N, a->K, a->epilogue, kpb, p.rows_per_batch, p.valid_rows);
         if (mode == 3) return sbn;
         if (mode == 2) return sbn && sliced_rows_are_gemv(a->K, a->N, p.valid_rows) && p.valid_rows < p.rows_per_batch ? 1 : 0;
-        if (sbn) return launch_sliced_gemm(a, sbn, p.rows_per_batch, p.valid_rows, st0, algo == DGS_GEMM_QUAD, mode == 1);
+        if (sbn) return launch_sliced_gemm(p, a->epilogue, sbn, st0, algo == DGS_GEMM_QUAD, mode == 1);
     }
     if (mode == 2 || mode == 3) return 0;
     if (mode == 1) return DGS_ERR_INVALID_ARGUMENT;
@@ -412,7 +310,7 @@ static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode)
     const bool few_tiles = (a->M / BM) * (a->N / 128) < 512 && a->N % 128 == 0;
     if ((algo == DGS_GEMM_SLICED128 || (algo == DGS_GEMM_AUTO && few_tiles && !no_s128 && a->K >= s128_mink)) &&
         sliced128_eligible(a->M, a->N, a->K, a->epilogue, kpb, p.rows_per_batch))
-        return launch_sliced_gemm(a, -128, p.rows_per_batch, p.valid_rows, st0, false, false);
+        return launch_sliced_gemm(p, a->epilogue, -128, st0, false, false);
     // 128 x 64 tiles when 128 x 128 would leave the 256 CUs with fewer than two workgroups each
     if (a->epilogue == DGS_EPI_QKV && a->N % 128) return DGS_ERR_INVALID_ARGUMENT;
     static const int env_bn = getenv("DGS_GEMM_BN") ? atoi(getenv("DGS_GEMM_BN")) : 0;      // measurement aid
@@ -421,12 +319,12 @@ static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode)
     if (env_bn == 64) bn = 64;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (a->epilogue) {
-        case DGS_EPI_BF16: launch_gemm<DGS_EPI_BF16>(p, bn, st); break;
-        case DGS_EPI_GELU_BF16: launch_gemm<DGS_EPI_GELU_BF16>(p, bn, st); break;
-        case DGS_EPI_GATE_RESIDUAL: launch_gemm<DGS_EPI_GATE_RESIDUAL>(p, bn, st); break;
-        case DGS_EPI_F32: launch_gemm<DGS_EPI_F32>(p, bn, st); break;
-        case DGS_EPI_QKV: launch_gemm<DGS_EPI_QKV>(p, 128, st); break;
-        case DGS_EPI_DGELU_BF16: launch_gemm<DGS_EPI_DGELU_BF16>(p, bn, st); break;
+        case DGS_EPI_BF16: launch_gemm<DGS_EPI_BF16>(p, kpb, bn, st); break;
+        case DGS_EPI_GELU_BF16: launch_gemm<DGS_EPI_GELU_BF16>(p, kpb, bn, st); break;
+        case DGS_EPI_GATE_RESIDUAL: launch_gemm<DGS_EPI_GATE_RESIDUAL>(p, kpb, bn, st); break;
+        case DGS_EPI_F32: launch_gemm<DGS_EPI_F32>(p, kpb, bn, st); break;
+        case DGS_EPI_QKV: launch_gemm<DGS_EPI_QKV>(p, kpb, 128, st); break;
+        case DGS_EPI_DGELU_BF16: launch_gemm<DGS_EPI_DGELU_BF16>(p, kpb, bn, st); break;
         default: return DGS_ERR_INVALID_ARGUMENT;
     }
     return hipGetLastError() == hipSuccess ? DGS_OK : DGS_ERR_DEVICE;

@@ -19,26 +19,19 @@
 
 namespace dgs {
 
-struct DeepParams {
-    int M, N, K, lda, ldw, ldo, gate_stride, rows_per_batch, valid_rows, tiles_n, ntiles, dbg;
+struct DeepParams : GemmCore {
+    int tiles_n, ntiles, dbg;
     int rows_ps, full_rows, tail_rows, nfull_items;             // sliced kernel: 256-row tile rows per sample (all / ring path / one live block), full items
     int ntail, tail_mode;                                       // sliced kernel: side jobs of the single-live-block tile rows (1: MFMA items, 2: two-row GEMV items)
     int tail_wgs;                                               // > 0: that many workgroups BEHIND the tiles do nothing but the side jobs (idle CUs)
     int map2d;                                                  // tile <- workgroup id: 4 x 2 blocks of the tile grid per XCD (launch_sliced decides)
     int rows_external;                                          // the two-row GEMV side jobs are somebody else's work (layernorm_rows_gemv_kernel): none here
     int nsplit, splits_per_batch;                               // sliced kernel, split-K: items = nsplit x tiles, K = k_per_batch
-    long long a_batch_stride, w_batch_stride, out_split_stride;
-    const bf16_t* A;
-    const bf16_t* W;
-    const float* bias;
-    void* out;
-    const float* gate;
-    const float* resid;
-    bf16_t* vt;
-    void* aux;
-    float q_scale;
+    long long out_split_stride;
 };
 
+// GELU-tanh and its derivative in the __expf + IEEE division form.  store_block below is the one place that still uses it; everything
+// else, the rest of the same output tensor included, goes through epi_gelu_tanh / epi_dgelu_tanh (dit_gemm_epilogue.h).
 __device__ __forceinline__ float gelu_tanh_d(float x) {
     const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
     return x / (1.0f + __expf(-2.0f * u));
@@ -57,54 +50,53 @@ __device__ __forceinline__ int slab_off(int r, int c) {
     return BK == 64 ? r * 128 + ((c ^ ((r >> 1) & 7)) << 4) : r * 64 + ((c ^ ((r >> 2) & 3)) << 4);
 }
 
-template <int EPI, int NI>
-__device__ __forceinline__ void store_block(const DeepParams& p, const f32x16 (&acc)[NI], int mbase, int nbase, int lane) {
-    // D fragment: col (n) = lane & 31, row (m) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); mbase already includes 4 * (lane >> 5)
+// The store of one 32 x 32 block of a single-block MFMA side item (tail_mode 1), straight from the D fragment: a lane holds column
+// n (the block's first + lane & 31) and rows (r & 3) + 8 (r >> 2) of mbase, which already includes 4 * (lane >> 5).
+// Not store_strip: these few blocks keep the per-register epilogue every tile once had, with gelu_tanh_d where store_strip has
+// epi_gelu_tanh.  Moving them to store_strip changes output bits, so it is a decision of its own and not part of a refactor.
+template <int EPI>
+__device__ __forceinline__ void store_block(const DeepParams& p, const f32x16& acc, int mbase, int n) {
     const int b = mbase / p.rows_per_batch;
+    const float bias = p.bias ? p.bias[n] : 0.0f;
+    const float qs = (EPI == DGS_EPI_QKV && n < p.N / 3) ? p.q_scale : 1.0f;      // pre-scaled queries
+    const bool qkv_v = EPI == DGS_EPI_QKV && n >= (p.N / 3) * 2;
+    bf16_t* tdst = nullptr;
+    if (EPI == DGS_EPI_QKV) {
+        if (qkv_v) tdst = p.vt + ((size_t)b * (p.N / 3) + (n - (p.N / 3) * 2)) * p.rows_per_batch + (mbase - b * p.rows_per_batch);
+    } else if ((EPI == DGS_EPI_BF16 || EPI == DGS_EPI_GELU_BF16 || EPI == DGS_EPI_DGELU_BF16) && p.vt) {
+        tdst = p.vt + ((size_t)b * p.N + n) * p.rows_per_batch + (mbase - b * p.rows_per_batch);
+    }
+    float gate = 0.0f;
+    if (EPI == DGS_EPI_GATE_RESIDUAL) gate = p.gate[(size_t)b * p.gate_stride + n];
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-        const int n = nbase + ni * 32 + (lane & 31);
-        const float bias = p.bias ? p.bias[n] : 0.0f;
-        const float qs = (EPI == DGS_EPI_QKV && n < p.N / 3) ? p.q_scale : 1.0f;      // pre-scaled queries
-        const bool qkv_v = EPI == DGS_EPI_QKV && n >= (p.N / 3) * 2;
-        bf16_t* tdst = nullptr;
-        if (EPI == DGS_EPI_QKV) {
-            if (qkv_v) tdst = p.vt + ((size_t)b * (p.N / 3) + (n - (p.N / 3) * 2)) * p.rows_per_batch + (mbase - b * p.rows_per_batch);
-        } else if ((EPI == DGS_EPI_BF16 || EPI == DGS_EPI_GELU_BF16 || EPI == DGS_EPI_DGELU_BF16) && p.vt) {
-            tdst = p.vt + ((size_t)b * p.N + n) * p.rows_per_batch + (mbase - b * p.rows_per_batch);
-        }
-        float gate = 0.0f;
-        if (EPI == DGS_EPI_GATE_RESIDUAL) gate = p.gate[(size_t)b * p.gate_stride + n];
+    for (int g = 0; g < 4; ++g) {
+        float o4[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float o4[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int m = mbase + q + 8 * g;
-                const float v = EPI == DGS_EPI_QKV ? (acc[ni][4 * g + q] + bias) * qs : acc[ni][4 * g + q] + bias;
-                const size_t o = (size_t)m * p.ldo + n;
-                if (EPI == DGS_EPI_BF16) {
-                    o4[q] = v;
-                    reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(v);
-                } else if (EPI == DGS_EPI_QKV) {
-                    o4[q] = v;
-                    if (!qkv_v) reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(v);
-                } else if (EPI == DGS_EPI_GELU_BF16) {
-                    o4[q] = gelu_tanh_d(v);
-                    reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(o4[q]);
-                    if (p.aux) reinterpret_cast<bf16_t*>(p.aux)[o] = (bf16_t)f2bf_fast(v);
-                } else if (EPI == DGS_EPI_DGELU_BF16) {
-                    o4[q] = v * dgelu_tanh_d(bf2f(reinterpret_cast<const bf16_t*>(p.aux)[o]));
-                    reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(o4[q]);
-                } else if (EPI == DGS_EPI_GATE_RESIDUAL) {
-                    reinterpret_cast<float*>(p.out)[o] = p.resid[o] + gate * v;
-                    if (p.aux) reinterpret_cast<bf16_t*>(p.aux)[o] = (bf16_t)f2bf_fast(v);
-                } else {
-                    reinterpret_cast<float*>(p.out)[o] = v;
-                }
+        for (int q = 0; q < 4; ++q) {
+            const int m = mbase + q + 8 * g;
+            const float v = EPI == DGS_EPI_QKV ? (acc[4 * g + q] + bias) * qs : acc[4 * g + q] + bias;
+            const size_t o = (size_t)m * p.ldo + n;
+            if (EPI == DGS_EPI_BF16) {
+                o4[q] = v;
+                reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(v);
+            } else if (EPI == DGS_EPI_QKV) {
+                o4[q] = v;
+                if (!qkv_v) reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(v);
+            } else if (EPI == DGS_EPI_GELU_BF16) {
+                o4[q] = gelu_tanh_d(v);
+                reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(o4[q]);
+                if (p.aux) reinterpret_cast<bf16_t*>(p.aux)[o] = (bf16_t)f2bf_fast(v);
+            } else if (EPI == DGS_EPI_DGELU_BF16) {
+                o4[q] = v * dgelu_tanh_d(bf2f(reinterpret_cast<const bf16_t*>(p.aux)[o]));
+                reinterpret_cast<bf16_t*>(p.out)[o] = (bf16_t)f2bf_fast(o4[q]);
+            } else if (EPI == DGS_EPI_GATE_RESIDUAL) {
+                reinterpret_cast<float*>(p.out)[o] = p.resid[o] + gate * v;
+                if (p.aux) reinterpret_cast<bf16_t*>(p.aux)[o] = (bf16_t)f2bf_fast(v);
+            } else {
+                reinterpret_cast<float*>(p.out)[o] = v;
             }
-            if (tdst) *reinterpret_cast<uint2*>(tdst + 8 * g) = make_uint2(pack_bf2(o4[0], o4[1]), pack_bf2(o4[2], o4[3]));
         }
+        if (tdst) *reinterpret_cast<uint2*>(tdst + 8 * g) = make_uint2(pack_bf2(o4[0], o4[1]), pack_bf2(o4[2], o4[3]));
     }
 }
 
@@ -120,11 +112,6 @@ __device__ __forceinline__ void store_block(const DeepParams& p, const f32x16 (&
 // with sched_barrier fences between { 1 MFMA, <= 1 LDS read } slices so the order in the source is the issue order.
 // The slab loop is unrolled by the ring depth: ring slots are literals and every LDS address is register + immediate.
 // ------------------------------------------------------------------------------------------------------------------
-template <int I> struct SIC { static constexpr int value = I; };
-template <int I, int N, class F> __device__ __forceinline__ void sliced_for(F&& f) {
-    if constexpr (I < N) { f(SIC<I>{}); sliced_for<I + 1, N>(f); }
-}
-
 __device__ long long dgs_gemm_dbg[16];   // DGS_GEMM_DBG: cycle stamps of workgroup 0, wave 0 (loop total, wait + barrier share)
 __device__ unsigned dgs_gemm_tl[1024][4]; // DGS_GEMM_DBG: per workgroup {start, loop start, loop end, end} on the constant 100 MHz clock (low 32 bits)
 
@@ -181,7 +168,7 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
             // item is 8 output columns of one sample and ONE memory round trip: the NW waves split K, every wave issues all of its
             // loads (8 columns x its K range, 16 bytes per lane; a wave-instruction = 1 KiB of one row = 8 cache lines, against the
             // 32 lines of a fragment-layout gather) before the first v_dot2c_f32_bf16; the partial sums meet in LDS and 16 lanes
-            // apply the epilogue element-wise (tail_store).  While the chip streams GEMM tiles a round trip costs microseconds:
+            // apply the epilogue element-wise (the shared item code of dit_gemm_epilogue.h).  While the chip streams GEMM tiles a round trip costs microseconds:
             // the earlier form (a wave per 32 / NW columns, all of K, two columns per trip) held its workgroup back by 13 us at K = 4096.
             // The NW waves are KS ranges of K x CS groups of 8 columns: KS = min(NW, K / 512) keeps every lane of a wave busy
             // (a range is 512 or 1024 elements = one or two 16-byte loads per lane and row).
@@ -190,18 +177,14 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
             const int kq = wave % KS, cq = wave / KS;
             const int kw = K_all / KS, k_lo = kq * kw;                   // 512 or 1024
             const bool two = kw > 512;
-            float* const part = reinterpret_cast<float*>(lds + (NS - 1) * STAGE);     // [k range][row][column of the item]
             const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+            float* const part = reinterpret_cast<float*>(lds + (NS - 1) * STAGE);     // [k range][row][column of the item]
             for (int j = first; j < p.ntail; j += stride) {
                 const int blk = j % nblk, trr = j / nblk;
                 const int tm0 = ((trr / p.tail_rows) * p.rows_ps + p.full_rows + trr % p.tail_rows) * BM, tn0 = blk * CPI + cq * 8;
+                const Gemv2Element<EPI> e(p, tid, CPI, tm0, blk * CPI, p.valid_rows - (tm0 - (tm0 / p.rows_per_batch) * p.rows_per_batch));
                 const bf16_t* a_row0 = A_all + (size_t)tm0 * p.lda + k_lo + lane * 8;
                 const bf16_t* w_col0 = W_all + (size_t)tn0 * p.ldw + k_lo + lane * 8;
-                const int er = tid / CPI, ec = tid - er * CPI;           // the element thread `tid` finishes (tid < 2 CPI)
-                const int erow = tm0 + er;
-                const bool finisher = tid < 2 * CPI && erow - (erow / p.rows_per_batch) * p.rows_per_batch < p.valid_rows;
-                TailOperands ops{0.f, 0.f, 0.f};
-                if (finisher) ops = tail_prefetch<EPI>(p, erow, blk * CPI + ec);
                 uint4 a[2][2], w[8][2];
 #pragma unroll
                 for (int ch = 0; ch < 2; ++ch) {
@@ -211,18 +194,12 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
 #pragma unroll
                     for (int c = 0; c < 8; ++c) w[c][ch] = on ? *reinterpret_cast<const uint4*>(w_col0 + (size_t)c * p.ldw + ch * 512) : zero;
                 }
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    float s0 = dot8_bf16(a[0][0], w[c][0], 0.f), s1 = dot8_bf16(a[1][0], w[c][0], 0.f);
-                    s0 = dot8_bf16(a[0][1], w[c][1], s0); s1 = dot8_bf16(a[1][1], w[c][1], s1);
-                    s0 = wave_sum_lane63(s0); s1 = wave_sum_lane63(s1);
-                    if (lane == 63) { part[(kq * 2 + 0) * CPI + cq * 8 + c] = s0; part[(kq * 2 + 1) * CPI + cq * 8 + c] = s1; }
-                }
+                gemv2_partials<2>(a, w, part, kq, CPI, cq * 8, lane);
                 __syncthreads();
-                if (finisher) {
+                if (e.on) {
                     float v = 0.f;
-                    for (int q = 0; q < KS; ++q) v += part[(q * 2 + er) * CPI + ec];
-                    tail_store<EPI>(p, erow, blk * CPI + ec, v, ops);
+                    for (int q = 0; q < KS; ++q) v += e.partial(part, q);
+                    e.store(p, v);
                 }
                 __syncthreads();
             }
@@ -235,24 +212,24 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
             const int cbl = wave % CBW, kq = wave / CBW, kper = K_all / KQ;  // kper % 128 == 0 (launch_sliced)
             const bf16_t* arow = A_all + (size_t)(tm0 + frow) * p.lda + kq * kper + fhalf * 8;
             const bf16_t* wrow = W_all + (size_t)(tn0 + cbl * 32 + frow) * p.ldw + kq * kper + fhalf * 8;
-            f32x16 acc1[1];
+            f32x16 acc1;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[0][r] = 0.f;
+            for (int r = 0; r < 16; ++r) acc1[r] = 0.f;
             if (kper % 256 == 0)
-                for (int k = 0; k < kper; k += 256) direct_block_mfma<16>(arow + k, wrow + k, acc1[0]);
+                for (int k = 0; k < kper; k += 256) direct_block_mfma<16>(arow + k, wrow + k, acc1);
             else
-                for (int k = 0; k < kper; k += 128) direct_block_mfma<8>(arow + k, wrow + k, acc1[0]);
+                for (int k = 0; k < kper; k += 128) direct_block_mfma<8>(arow + k, wrow + k, acc1);
             float* red = reinterpret_cast<float*>(lds + (NS - 1) * STAGE);          // (KQ - 1) * CBW * 4 KiB <= STAGE
             if (kq > 0)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) red[((kq - 1) * CBW + cbl) * 1024 + r * 64 + lane] = acc1[0][r];
+                for (int r = 0; r < 16; ++r) red[((kq - 1) * CBW + cbl) * 1024 + r * 64 + lane] = acc1[r];
             __syncthreads();
             if (kq == 0) {
 #pragma unroll
                 for (int q = 1; q < KQ; ++q)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) acc1[0][r] += red[((q - 1) * CBW + cbl) * 1024 + r * 64 + lane];
-                store_block<EPI, 1>(p, acc1, tm0 + 4 * fhalf, tn0 + cbl * 32, lane);
+                    for (int r = 0; r < 16; ++r) acc1[r] += red[((q - 1) * CBW + cbl) * 1024 + r * 64 + lane];
+                store_block<EPI>(p, acc1, tm0 + 4 * fhalf, tn0 + cbl * 32 + frow);
             }
             __syncthreads();                                            // `red` is rewritten by the next item / the ring
         }
@@ -338,15 +315,15 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
         else lds_dma_scalar<slot * STAGE + A_BYTES + NW * (q - GA) * 1024>(sb_w, vo_w[q - GA], lds_wave, lds_mine);
         if constexpr (q == G - 1) { sb_a += 2 * BK * KW; sb_w += 2 * BK * KW; }
     };
-    auto stage_next = [&](auto slotc) { sliced_for<0, G>([&](auto qc) { dma_piece(slotc, qc); }); };
+    auto stage_next = [&](auto slotc) { static_for<0, G>([&](auto qc) { dma_piece(slotc, qc); }); };
     // ---- prologue: slabs 0 .. NS-2 in flight, then the fragments of slab 0, substep 0.  A workgroup with a side job issues only
     //      slabs 0 and 1 first: vector memory returns in order, and behind all NS-1 slabs (112 KiB with the 8-stage ring) the side
     //      job's one round trip became ~10 k cycles; the other slabs go out when the side job is done ----
     //      (8-stage ring only: fc2 +2.4 -> +1.0 us for the two learned-token rows; with the 4-stage ring there is one slab to hold
     //      back, and holding it back costs more than it saves: fc1 +4.1 -> +5.4)
     const bool has_side_job = NS > 4 && p.tail_wgs == 0 && bid < p.ntail && p.nsplit == 1;
-    sliced_for<0, 2>([&](auto sc) { stage_next(sc); });
-    if (!has_side_job) sliced_for<2, NS - 1>([&](auto sc) { stage_next(sc); });
+    static_for<0, 2>([&](auto sc) { stage_next(sc); });
+    if (!has_side_job) static_for<2, NS - 1>([&](auto sc) { stage_next(sc); });
     // ---- tiles with a single live 32-row block (the learned-token rows of every sample), folded into the first workgroups ----
     // An item is 32 rows x 32 columns (64 for BN = 128): the NW waves are ranges of K, every wave pulls its fragments straight from
     // L2 in one round trip per 128 / 256 columns of K (one trip for K = 1024), the ranges meet in the ring stage that iteration 0
@@ -356,7 +333,7 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
     // 256 CUs, so they start when the first full tiles retire) these items added 36 us when a wave walked all of K for one
     // column block, and still 14 us in this one-trip form.
     if (p.tail_wgs == 0) side_jobs(bid, (int)gridDim.x);
-    if (has_side_job) sliced_for<2, NS - 1>([&](auto sc) { stage_next(sc); });
+    if (has_side_job) static_for<2, NS - 1>([&](auto sc) { stage_next(sc); });
     // Slabs 0 and 1 have to be there before iteration 0 (its second half prefetches fragments of slab 1); slabs 2 .. NS-2 may stay
     // in flight -- with the 8-stage ring of the 128 x 128 tiles, waiting for all seven (112 KiB per CU, every CU at once) cost
     // ~10 k cycles of every tile.  Stores a side job left in flight are older than those slabs: "at most (NS-3) G operations
@@ -387,8 +364,8 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
         constexpr int slot = decltype(slot_tag)::value;
         constexpr int PRE_N = decltype(pre_tag)::value;                // residual loads in flight at the end of this iteration
         constexpr bool refill = decltype(refill_tag)::value;           // slab t + NS - 1 exists; it goes into the stage of slab t - 1
-        if constexpr (refill && !SPREAD && EXP != 1) stage_next(SIC<(slot + NS - 1) % NS>{});
-        sliced_for<0, 2 * MF>([&](auto jc) {
+        if constexpr (refill && !SPREAD && EXP != 1) stage_next(IC<(slot + NS - 1) % NS>{});
+        static_for<0, 2 * MF>([&](auto jc) {
             constexpr int J = decltype(jc)::value, ks = J / MF, i = (J % MF) / NI, j = J % NI;
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[ks][i], fr[ks][WMB + j], acc[i][j], 0, 0, 0);
             sched_fence();                                         // the MFMA leads its slice: what follows issues in its shadow
@@ -397,7 +374,7 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
             if constexpr (f < NF && EXP != 2) fr[ks ^ 1][f] = frag(ks == 0 ? slot : (slot + 1) % NS, ks ^ 1, f);
             if constexpr (SPREAD && refill && ks == 0 && f >= MF - G && EXP != 1) {
                 constexpr int q = f - (MF - G);
-                dma_piece(SIC<(slot + NS - 1) % NS>{}, SIC<q>{});
+                dma_piece(IC<(slot + NS - 1) % NS>{}, IC<q>{});
             }
             sched_fence();
         });
@@ -436,10 +413,10 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
     const long long dbg_w1 = dbg == 1 ? wall_stamp() : 0;
     auto k_loop = [&](auto dbg_tag) {
         for (int t = 0; t < nk - NS; t += NS)                      // unrolled by the ring depth: slots are literals
-            sliced_for<0, NS>([&](auto sc) { iteration(t + decltype(sc)::value, sc, std::true_type{}, SIC<0>{}, SIC<0>{}, dbg_tag); });
-        sliced_for<0, NS>([&](auto sc) {                           // the last slab goes out in the first of the last NS iterations
+            static_for<0, NS>([&](auto sc) { iteration(t + decltype(sc)::value, sc, std::true_type{}, IC<0>{}, IC<0>{}, dbg_tag); });
+        static_for<0, NS>([&](auto sc) {                           // the last slab goes out in the first of the last NS iterations
             constexpr int S = decltype(sc)::value;
-            iteration(nk - NS + S, sc, std::integral_constant<bool, S == 0>{}, SIC<PRE_LOADS>{}, SIC<(NS - S - 3 > 0 ? NS - S - 3 : 0)>{}, dbg_tag);
+            iteration(nk - NS + S, sc, std::integral_constant<bool, S == 0>{}, IC<PRE_LOADS>{}, IC<(NS - S - 3 > 0 ? NS - S - 3 : 0)>{}, dbg_tag);
         });
     };
     if constexpr (kInstrumented) {
@@ -480,8 +457,7 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
             if constexpr (PREFETCH_RESID) store_strip<EPI, 2>(p, &acc[1][0], mb, nb, lane, patch, pre[0]);
             else store_strip<EPI, 2>(p, &acc[1][0], mb, nb, lane, patch);
         }
-    } else
-    if (epi_staged<EPI>(p)) {          // the ring is idle now (everybody passed the last barrier): a private LDS patch per wave
+    } else {                           // the ring is idle now (everybody passed the last barrier): a private LDS patch per wave
         char* patch = lds + wave * epi_strip_bytes(2);
         if constexpr (NI % 2 == 1) {
             // three column blocks (BN = 192): a two-block strip and a single one; store_strip decides "V feature" per strip, so the one
@@ -503,9 +479,6 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
                 if constexpr (PREFETCH_RESID) store_strip<EPI, 2>(p, &acc[i][j], m0 + wm * WROWS + 32 * i, n0 + wn * WN + 32 * j, lane, patch, pre[i * (NI / 2) + j / 2]);
                 else store_strip<EPI, 2>(p, &acc[i][j], m0 + wm * WROWS + 32 * i, n0 + wn * WN + 32 * j, lane, patch);
             }
-    } else {
-#pragma unroll
-        for (int i = 0; i < WMB; ++i) store_block<EPI, NI>(p, acc[i], m0 + wm * WROWS + 32 * i + 4 * fhalf, n0 + wn * WN, lane);
     }
     if constexpr (kInstrumented) if (dbg == 1) {
         wait_vmcnt<0>();
@@ -654,20 +627,16 @@ bool sliced_rows_are_gemv(int K, int N, int valid_rows) {
     return last_live <= 2 && K >= 512 && K <= 4096 && (K & (K - 1)) == 0 && N % 64 == 0;
 }
 
-int launch_sliced_gemm(const DgsDitGemmArgs* a, int bn, int rows_per_batch, int valid_rows, hipStream_t st, bool quad, bool rows_external) {
+int launch_sliced_gemm(const GemmCore& c, int epilogue, int bn, hipStream_t st, bool quad, bool rows_external) {
     DeepParams p;
+    static_cast<GemmCore&>(p) = c;
     p.rows_external = rows_external ? 1 : 0;
-    p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldw = a->ldw; p.ldo = a->ldo; p.gate_stride = a->gate_stride;
-    p.rows_per_batch = rows_per_batch; p.valid_rows = valid_rows; p.dbg = 0; p.nsplit = 1; p.splits_per_batch = 1;
-    p.a_batch_stride = p.w_batch_stride = p.out_split_stride = 0;
-    p.A = a->A; p.W = a->W; p.bias = a->bias; p.out = a->out; p.gate = a->gate; p.vt = a->vt; p.aux = a->aux;
-    p.q_scale = a->q_scale != 0.0f ? a->q_scale : 1.0f;
-    p.resid = a->resid ? a->resid : static_cast<const float*>(a->out);
+    p.dbg = 0; p.nsplit = 1; p.splits_per_batch = 1; p.out_split_stride = 0;
     static const int s128_nw4 = getenv("DGS_GEMM_S128_NW4") ? atoi(getenv("DGS_GEMM_S128_NW4")) : 0;   // measurement aid: the 4-wave form of the 128 x 128 tile
 #define DGS_SLICED_CASE(E) case E: return bn == 256 ? (quad ? launch_sliced<E, 256, 4>(p, st) : launch_sliced<E, 256>(p, st)) : \
                                    bn == 128 ? launch_sliced<E, 128>(p, st) : s128_nw4 ? launch_sliced<E, 128, 4, 128>(p, st) : launch_sliced<E, 128, 8, 128>(p, st)
-    if (bn == 192) return a->epilogue == DGS_EPI_QKV && !quad ? launch_sliced<DGS_EPI_QKV, 192>(p, st) : DGS_ERR_INVALID_ARGUMENT;
-    switch (a->epilogue) {
+    if (bn == 192) return epilogue == DGS_EPI_QKV && !quad ? launch_sliced<DGS_EPI_QKV, 192>(p, st) : DGS_ERR_INVALID_ARGUMENT;
+    switch (epilogue) {
         DGS_SLICED_CASE(DGS_EPI_BF16);
         DGS_SLICED_CASE(DGS_EPI_GELU_BF16);
         DGS_SLICED_CASE(DGS_EPI_GATE_RESIDUAL);
@@ -718,11 +687,10 @@ int launch_splitk_gemm(const DgsDitGemmArgs* a, int k_per_batch, hipStream_t st)
     const int nsplit = splitk_plan(a->M, a->N, a->K, k_per_batch, &spb);
     if (!nsplit || a->epilogue != DGS_EPI_F32 || a->bias || !a->splitk_ws || a->ldo % 4) return DGS_ERR_INVALID_ARGUMENT;
     DeepParams p;
-    p.M = a->M; p.N = a->N; p.K = k_per_batch; p.lda = a->lda; p.ldw = a->ldw; p.ldo = a->N; p.gate_stride = 0;
-    p.rows_per_batch = a->M; p.valid_rows = a->M; p.dbg = 0; p.nsplit = nsplit; p.splits_per_batch = spb;
-    p.a_batch_stride = a->a_batch_stride; p.w_batch_stride = a->w_batch_stride; p.out_split_stride = (long long)a->M * a->N;
-    p.A = a->A; p.W = a->W; p.bias = nullptr; p.out = a->splitk_ws; p.gate = nullptr; p.vt = nullptr; p.aux = nullptr; p.q_scale = 1.0f;
-    p.resid = nullptr; p.rows_external = 0;
+    static_cast<GemmCore&>(p) = gemm_core(a);
+    // one "sample" of M rows whose reduction is one sample's K; the partial products go to the scratch planes, dense [M, N]
+    p.K = k_per_batch; p.rows_per_batch = p.valid_rows = a->M; p.out = a->splitk_ws; p.ldo = a->N;
+    p.dbg = 0; p.nsplit = nsplit; p.splits_per_batch = spb; p.out_split_stride = (long long)a->M * a->N; p.rows_external = 0;
     const int rc = launch_sliced<DGS_EPI_F32, 256>(p, st);
     if (rc != DGS_OK) return rc;
     const size_t plane = (size_t)a->M * a->N;

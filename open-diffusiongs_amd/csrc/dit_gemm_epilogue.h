@@ -8,8 +8,7 @@
 // every lane stores 16 contiguous bytes (8 bf16 or 4 fp32) and the residual / gate / aux operands are 16-byte loads too:
 // 2-4 store instructions per block instead of 16.
 #pragma once
-#include "dit_common.h"
-#include "dgs_dit.h"
+#include "dit_kernels.h"
 
 namespace dgs {
 
@@ -46,22 +45,6 @@ __device__ __forceinline__ void direct_block_mfma(const bf16_t* arow, const bf16
     for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u], w[u], acc, 0, 0, 0);
 }
 
-// dot product of 8 bf16 pairs held in two 16-byte registers, fp32 accumulate (v_dot2c_f32_bf16)
-__device__ __forceinline__ float dot8_bf16(const uint4& a, const uint4& b, float acc) {
-#ifdef HIPEMU
-    const unsigned x[4] = {a.x, a.y, a.z, a.w}, y[4] = {b.x, b.y, b.z, b.w};
-    for (int i = 0; i < 4; ++i)
-        acc += __uint_as_float(x[i] << 16) * __uint_as_float(y[i] << 16) + __uint_as_float(x[i] & 0xffff0000u) * __uint_as_float(y[i] & 0xffff0000u);
-    return acc;
-#else
-    typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2_t, a.x), __builtin_bit_cast(bf2_t, b.x), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2_t, a.y), __builtin_bit_cast(bf2_t, b.y), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2_t, a.z), __builtin_bit_cast(bf2_t, b.z), acc, false);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2_t, a.w), __builtin_bit_cast(bf2_t, b.w), acc, false);
-#endif
-}
-
 // Transposed copies ([feature][token], a lane owns ONE feature): the D-fragment layout gives lane (c, half) the tokens
 // 8 g + 4 half + {0..3} of its feature, i.e. 8-byte pieces; 32 features per wave-instruction = 32 cache lines for 512 bytes, and the
 // V third of the QKV tiles (and every tile of the training forward) left through four such instructions per block.  A half-wave
@@ -76,13 +59,9 @@ __device__ __forceinline__ void store_token_octet(bf16_t* tdst, int g, int half,
 
 constexpr int epi_strip_bytes(int nb) { return 32 * (32 * nb + 4) * 4; }     // LDS per wave
 
-
-// Which (epilogue, arguments) take the staged path: all of them.  (The training epilogues -- DGELU and the transposed `vt`
-// copies of BF16 / GELU / DGELU -- used to keep the per-register path of their kernel: 16 two-byte loads and stores per block
-// per lane made the fc2 input-gradient GEMM 489 us at 4 samples, 175 us more than the forward fc1 of the same shape.)
-template <int EPI, class P>
-__device__ __forceinline__ bool epi_staged(const P&) { return true; }
-
+// Every epilogue and every argument combination leaves through store_strip.  (The training epilogues -- DGELU and the transposed
+// `vt` copies of BF16 / GELU / DGELU -- once kept a per-register path: 16 two-byte loads and stores per block per lane made the fc2
+// input-gradient GEMM 489 us at 4 samples, 175 us more than the forward fc1 of the same shape.)
 // acc[0 .. NB): NB side-by-side 32 x 32 accumulator blocks: rows m0 .. m0+31 (m0 = first row of the block), columns
 // n0 .. n0 + 32 NB - 1.  `patch` = this wave's private LDS patch (epi_strip_bytes(NB) bytes); nobody else touches it, so no
 // barrier is needed -- LDS operations of one wave execute in order.
@@ -209,7 +188,7 @@ __device__ __forceinline__ void store_strip(const P& p, const f32x16* acc, int m
 }
 
 // One output element (row m, column n) through epilogue EPI: the scalar twin of store_strip, same arithmetic and roundings.
-// Used by the GEMV items that compute the one or two live rows behind a sample's last full tile.
+// Used by the two-row GEMV items below.
 struct TailOperands { float bias, resid, gate; };           // what a GEMV item can load BEFORE its dot products: no second round trip
 template <int EPI, class P>
 __device__ __forceinline__ TailOperands tail_prefetch(const P& p, int m, int n) {
@@ -249,5 +228,45 @@ __device__ __forceinline__ void tail_store(const P& p, int m, int n, float v, co
     if (p.vt) p.vt[((size_t)b * p.N + n) * p.rows_per_batch + (m - b * p.rows_per_batch)] = bf1(v);
 }
 
+// ---- The two-row GEMV item: the one or two live rows behind a sample's last full tile (the DiT's learned tokens) times 8 W columns
+//      per wave, on the vector pipe.  The waves of a workgroup are K ranges of `kw` elements (one or two 16-byte loads per lane and
+//      operand row) x groups of 8 columns; an item is `cpi` columns wide.  Its three users -- the 128-wide kernel's items behind its
+//      tiles (dit_gemm.hip), the ring kernel's side jobs (dit_gemm_deep.hip) and the first workgroups of the LayerNorm launch in front
+//      of a GEMM (dit_elementwise.hip) -- differ in where the A rows come from, in how they cut K and the columns over their waves, and
+//      in the order in which they add the K ranges' partial sums; everything else is here, so equal cuts and orders give equal bits.
+//      (The operand loads stay with the callers, word for word: hipcc's code for `on ? *ptr : zero` hangs on the form of `on` and on
+//      where the statement stands.  Through one shared loader the 128-wide kernel's 16-byte loads fell apart into 4-byte ones, or the
+//      ring kernel got scratch, or its 4-wave 128 x 128 form lost a wave per SIMD; a loader without the addressable zero gave both
+//      kernels clean 16-byte loads and made fc2 0.8 % slower on both.) ----
+
+// Operand registers -> part[k range kq][row][column c0 + c of the item]: the wave's sum over its K range, written by lane 63.
+template <int NCH>
+__device__ __forceinline__ void gemv2_partials(const uint4 (&a)[2][NCH], const uint4 (&w)[8][NCH], float* part, int kq, int cpi, int c0, int lane) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) { s0 = dot8_bf16(a[0][ch], w[c][ch], s0); s1 = dot8_bf16(a[1][ch], w[c][ch], s1); }
+        s0 = wave_sum_lane63(s0); s1 = wave_sum_lane63(s1);
+        if (lane == 63) { part[(kq * 2 + 0) * cpi + c0 + c] = s0; part[(kq * 2 + 1) * cpi + c0 + c] = s1; }
+    }
+}
+
+// The output element thread `tid` of the workgroup finishes: row tid / cpi (of `live` <= 2), column tid % cpi of the item whose first
+// element is (m0, n0).  Its epilogue operands are requested on construction, i.e. before the dot products: no second round trip.
+template <int EPI>
+struct Gemv2Element {
+    bool on;
+    int m, n, er, ec, cpi;
+    TailOperands ops;
+    __device__ __forceinline__ Gemv2Element(const GemmCore& p, int tid, int cpi_, int m0, int n0, int live) : cpi(cpi_), ops{0.f, 0.f, 0.f} {
+        er = tid / cpi; ec = tid - er * cpi;
+        on = tid < 2 * cpi && er < live;
+        m = m0 + er; n = n0 + ec;
+        if (on) ops = tail_prefetch<EPI>(p, m, n);
+    }
+    __device__ __forceinline__ float partial(const float* part, int kq) const { return part[(kq * 2 + er) * cpi + ec]; }
+    __device__ __forceinline__ void store(const GemmCore& p, float v) const { tail_store<EPI>(p, m, n, v, ops); }
+};
 
 }  // namespace dgs

@@ -33,16 +33,40 @@ struct GsParams {
     float *xyz, *features, *scaling, *rotation, *opacity, *aligned;
 };
 
+// What every DiT GEMM kernel and every epilogue (dit_gemm_epilogue.h) reads of a dgs_dit_gemm call; GemmParams (dit_gemm.hip) and
+// DeepParams (dit_gemm_deep.hip) add their kernel's work distribution to it.
+struct GemmCore {
+    int M, N, K, lda, ldw, ldo, gate_stride, rows_per_batch, valid_rows;
+    long long a_batch_stride, w_batch_stride;   // element stride between samples along the reduction (weight-gradient GEMMs)
+    const bf16_t* A;
+    const bf16_t* W;
+    const float* bias;
+    void* out;
+    const float* gate;
+    const float* resid;              // GATE_RESIDUAL input stream (== out for the in-place inference form)
+    bf16_t* vt;                      // transposed bf16 copy [batch, N, rows_per_batch] (QKV: V only)
+    void* aux;                       // GELU: u out; GATE_RESIDUAL: y out; DGELU: u in   (bf16 [M, ldo])
+    float q_scale;                   // QKV: factor on the q features
+};
+
+// The one place where the defaults of DgsDitGemmArgs are applied.
+inline GemmCore gemm_core(const DgsDitGemmArgs* a) {
+    GemmCore c;
+    c.M = a->M; c.N = a->N; c.K = a->K; c.lda = a->lda; c.ldw = a->ldw; c.ldo = a->ldo; c.gate_stride = a->gate_stride;
+    c.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : a->M;
+    c.valid_rows = (a->valid_rows > 0 && a->valid_rows < c.rows_per_batch) ? a->valid_rows : c.rows_per_batch;
+    c.a_batch_stride = a->a_batch_stride; c.w_batch_stride = a->w_batch_stride;
+    c.A = a->A; c.W = a->W; c.bias = a->bias; c.out = a->out; c.gate = a->gate; c.vt = a->vt; c.aux = a->aux;
+    c.resid = a->resid ? a->resid : static_cast<const float*>(a->out);
+    c.q_scale = a->q_scale != 0.0f ? a->q_scale : 1.0f;
+    return c;
+}
+
 // Second role of a LayerNorm + modulate launch: the consumer GEMM's output rows [row0, row0 + nrows) of every sample (nrows <= 2: the
 // rows behind the sample's last full 256-row tile), see layernorm_rows_gemv_kernel.  `items` is set by the launcher.
 struct LnRowsGemv {
-    const bf16_t* W;           // the GEMM's weight [N, ldw], K = the LayerNorm's width
-    const float* bias;
-    void* out;
-    void* aux;
-    bf16_t* vt;
-    int N, ldw, ldo, epilogue, row0, nrows, items;
-    float q_scale;
+    GemmCore g;                // the GEMM: K = the LayerNorm's width, A = its output
+    int row0, nrows, items;
 };
 
 int launch_layernorm(const DgsDitLayerNormArgs* a, hipStream_t st);

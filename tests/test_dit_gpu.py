@@ -84,6 +84,15 @@ def test_layernorm_gemm_pair_at_the_model_shape(width, N, qkv, B):
     _check_layernorm_gemm_pair(ops, DEV, width, N, qkv, valids=(4098, 4097), B=B, rpb=4352, algo=_native.GEMM_AUTO)
 
 
+@pytest.mark.parametrize("N", [768, 25344])
+def test_gemm_sliced_single_block_mfma_items(N):
+    """The ring kernel's single-block MFMA side items through every epilogue that reaches their store: on 128-wide tiles (N = 768), and
+    on 256-wide tiles, 8 and 4 waves (N = 25,344: 2 x 99 tiles of 256 x 256 fill the chip, and 2 x 132 of 256 x 192 do not fit it)."""
+    from dgs_amd.dit import DitOps
+    from test_dit_kernels_emu import _check_single_block_mfma_items
+    _check_single_block_mfma_items(DitOps(), DEV, N)
+
+
 @pytest.mark.parametrize("M,N,K", [(4224, 3072, 1024), (4224, 1024, 4096), (256, 896, 1024), (4224, 1024, 576)])
 def test_gemm_production_shapes(M, N, K):
     g = torch.Generator(device=DEV).manual_seed(M + N + K)

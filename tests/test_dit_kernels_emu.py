@@ -444,6 +444,65 @@ def test_layernorm_gemm_pair_moves_the_learned_token_rows(ops, width, N, qkv):
     _check_layernorm_gemm_pair(ops, "cpu", width, N, qkv)
 
 
+def _check_single_block_mfma_items(ops, dev, N):
+    """The ring kernel's single-block MFMA side items (a tile row with ONE live 32-row block that is more than two rows: L = 256 + 20)
+    keep a store of their own (store_block, dit_gemm_deep.hip): every epilogue that reaches it, against fp32 math on the live rows,
+    with the rows behind that block untouched.  GEMM_SLICED always, GEMM_QUAD where the shape gets the 256-wide tiles it needs.
+    That the second tile row is such an item and not a ring tile rests on launch_sliced: 20 live rows are more than the GEMV items take
+    (<= 2), and K = 1024 is a multiple of every kernel's NW / (1 | 2) * 128 (`mfma_ok`).  The output shows it too: a ring tile would
+    write all 256 rows of the tile row, a GEMV item only the live ones; the item writes exactly its 32-row block."""
+    g = torch.Generator(device=dev).manual_seed(276 + N)
+    B, rpb, valid, K, Wd = 2, 512, 276, 1024, N // 3
+    M = B * rpb
+    A = _bf(torch.randn(M, K, generator=g, device=dev))
+    W = _bf(torch.randn(N, K, generator=g, device=dev) * 0.1)
+    bias = torch.randn(N, generator=g, device=dev)
+    x0 = torch.randn(M, N, generator=g, device=dev)
+    gate = torch.randn(B, N, generator=g, device=dev)
+    ref = A.float() @ W.float().t() + bias
+    row = torch.arange(M, device=dev) % rpb
+    live, kept = row < valid, row >= 288                     # the live block of the second tile row ends at row 287
+    block_pad = (row >= valid) & (row < 288)                 # padding rows inside that block: every one written (any finite value)
+    tr = lambda t, n: t.reshape(B, rpb, n).transpose(1, 2)   # [sample][feature][token]
+    close = lambda a, b: torch.allclose(a.float()[live], b[live], atol=3e-2, rtol=1e-2)
+    close_t = lambda a, b: torch.allclose(a.float()[:, :, :valid], b[:, :, :valid], atol=3e-2, rtol=1e-2)
+    fill = lambda *s: torch.full(s, 7.0, dtype=torch.bfloat16, device=dev)
+    kw = dict(rows_per_batch=rpb, valid_rows=valid)
+    algos = [_native.GEMM_SLICED]
+    for algo in algos:
+        out = torch.full((M, N), 7.0, device=dev)
+        ops.gemm(A, W, bias, _native.EPI_F32, out=out, algo=algo, **kw)
+        tile = ops.last_gemm_sliced_tile
+        assert tile in (128, 192, 256), (algo, tile)         # the call ran on the ring kernel
+        if algo == _native.GEMM_QUAD:
+            assert tile == 256
+        elif tile == 256:
+            algos.append(_native.GEMM_QUAD)
+        assert torch.allclose(out[live], ref[live], atol=4e-3, rtol=1e-4), algo
+        assert bool((out[kept] == 7.0).all()) and bool((out[block_pad] != 7.0).any(1).all()), algo
+        x = x0.clone()
+        ops.gemm(A, W, bias, _native.EPI_GATE_RESIDUAL, out=x, gate=gate, algo=algo, **kw)
+        assert ops.last_gemm_sliced_tile == tile
+        want = x0 + gate.repeat_interleave(rpb, 0) * ref
+        assert torch.allclose(x[live], want[live], atol=6e-3, rtol=1e-4), algo
+        assert torch.equal(x[kept], x0[kept]), algo
+        out, aux, vt = fill(M, N), fill(M, N), fill(B, N, rpb)
+        ops.gemm(A, W, bias, _native.EPI_GELU_BF16, out=out, aux=aux, vt=vt, algo=algo, **kw)
+        assert ops.last_gemm_sliced_tile == tile
+        act = F.gelu(ref, approximate="tanh")
+        assert close(out, act) and close(aux, ref) and close_t(vt, tr(act, N)), algo
+        assert bool((out[kept] == 7.0).all()) and bool((aux[kept] == 7.0).all()) and bool((vt[:, :, 288:] == 7.0).all()), algo
+        qk, vt = fill(M, 2 * Wd), fill(B, Wd, rpb)
+        ops.gemm(A, W, bias, _native.EPI_QKV, out=qk, vt=vt, q_scale=0.5, algo=algo, **kw)
+        assert ops.last_gemm_sliced_tile in (128, 192, 256)   # QKV may get 192-wide tiles where the other epilogues get 128
+        assert close(qk[:, :Wd], 0.5 * ref[:, :Wd]) and close(qk[:, Wd:], ref[:, Wd:2 * Wd]) and close_t(vt, tr(ref[:, 2 * Wd:], Wd)), algo
+        assert bool((qk[kept] == 7.0).all()) and bool((vt[:, :, 288:] == 7.0).all()) and bool((qk[block_pad] != 7.0).any(1).all()), algo
+
+
+def test_gemm_sliced_single_block_mfma_items(ops):
+    _check_single_block_mfma_items(ops, "cpu", 768)
+
+
 def test_gemm_sliced_2d_xcd_map(ops, monkeypatch):
     """One tile per CU and a tile grid that splits 4 x 2 over the XCDs: the workgroup id -> tile map is blocks of the grid, not runs of
     rows (same tiles, every one exactly once: the output is prefilled, a tile done twice or never shows).  16 'CUs' on the emulator."""
