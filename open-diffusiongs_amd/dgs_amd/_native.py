@@ -483,8 +483,28 @@ def _declare_ema(L):
     return L
 
 
+class DgsMeshArgs(ctypes.Structure):
+    _fields_ = [("X", ctypes.c_int32), ("Y", ctypes.c_int32), ("Z", ctypes.c_int32), ("level", ctypes.c_float),
+                ("occ", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("vertices", ctypes.c_void_p), ("triangles", ctypes.c_void_p),
+                ("max_vertices", ctypes.c_int64), ("max_triangles", ctypes.c_int64), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_int64)]
+
+
+# every symbol include/dgs_mesh.h declares (checked by tests/test_mesh.py)
+MESH_SYMBOLS = ["dgs_marching_cubes_count", "dgs_marching_cubes_emit", "dgs_marching_cubes_workspace_bytes"]
+
+
+def _declare_mesh(L):
+    for name in ("dgs_marching_cubes_count", "dgs_marching_cubes_emit"):
+        getattr(L, name).restype = ctypes.c_int
+        getattr(L, name).argtypes = [ctypes.POINTER(DgsMeshArgs), ctypes.c_void_p]
+    L.dgs_marching_cubes_workspace_bytes.restype = ctypes.c_int64
+    L.dgs_marching_cubes_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    return L
+
+
 _declare_raster = _declare
 
 
-def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA prototypes on one library)
-    return _declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L)))))))
+def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh prototypes on one library)
+    return _declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L))))))))

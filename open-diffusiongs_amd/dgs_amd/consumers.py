@@ -9,6 +9,8 @@ Mirrors diffusionGS/models/gsrenderer/gs_core.py:
                                                              f_dc_*, f_rest_* padded to SH degree 3, opacity, scale_*, rot_*)
     GaussianModel.extract_fields               :786-852     (reference: a host loop over num_blocks^3 blocks, ~15 torch ops and a
                                                              synchronisation each; here one C call, csrc/field.hip)
+    GaussianModel.extract_mesh                 :855-860     (reference: occ to the host, `mcubes.marching_cubes`; here two C calls on
+                                                             the device grid, csrc/mesh.hip, and a two-integer readback between them)
 The reference writes / reads the file through the `plyfile` package (binary_little_endian 1.0, one "vertex" element, scalar
 properties in dtype order); that byte layout is restated here with numpy structured arrays -- no extra dependency.
 """
@@ -226,3 +228,105 @@ def extract_fields(pc, resolution=128, num_blocks=16, relax_ratio=1.5, lib=None)
             for t in (xyzs, scaling, rotation, opacity, lin, lo, hi, ws):
                 t.record_stream(torch.cuda.current_stream(dev))
     return occ
+
+
+class Mesh:
+    """What GaussianModel.extract_mesh returns: vertices float32 [V, 3] in the reference's normalised cube [-1, 1]^3 and faces int32
+    [F, 3], both on the model's device (the reference wraps the same two arrays in a trimesh.Trimesh)."""
+
+    def __init__(self, vertices, faces):
+        self.vertices, self.faces = vertices, faces
+
+    def __repr__(self):
+        return f"Mesh(vertices={tuple(self.vertices.shape)}, faces={tuple(self.faces.shape)}, device={self.vertices.device})"
+
+
+def marching_cubes(occ, level, lib=None):
+    """The counterpart of `mcubes.marching_cubes(occ, level)` on occ's device: occ float32 [X, Y, Z] -> (vertices float32 [V, 3] in
+    index coordinates, triangles int32 [F, 3]), in the canonical order of include/dgs_mesh.h (csrc/mesh.hip); a sample is inside iff
+    occ > level.  dgs_marching_cubes_count, ONE readback of {V, F} to size the outputs, dgs_marching_cubes_emit; no crossing gives two
+    empty tensors."""
+    from . import _native
+    if occ.dim() != 3 or occ.dtype != torch.float32:
+        raise ValueError(f"marching_cubes: occ must be float32 [X, Y, Z], got {occ.dtype} {tuple(occ.shape)}")
+    with torch.no_grad():
+        occ = occ.detach().contiguous()
+        dev = occ.device
+        L = lib or _native.lib()
+        a = _native.DgsMeshArgs()
+        a.X, a.Y, a.Z = occ.shape
+        a.level = float(level)
+        a.workspace_bytes = L.dgs_marching_cubes_workspace_bytes(a.X, a.Y, a.Z)
+        if a.workspace_bytes <= 0:
+            raise ValueError(f"marching_cubes: unsupported grid {tuple(occ.shape)} (every axis >= 2, at most 2^30 samples)")
+        ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)              # the call writes uint32 [2]
+        a.occ, a.counts, a.workspace = (ctypes.c_void_p(t.data_ptr()) for t in (occ, counts, ws))
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if occ.is_cuda else None
+
+        def check(rc, name):
+            if rc != 0:
+                raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed: {rc} ({_native.status_string(L, rc)})")
+
+        check(L.dgs_marching_cubes_count(ctypes.byref(a), stream), "dgs_marching_cubes_count")
+        nv, nf = (c & 0xFFFFFFFF for c in counts.tolist())                  # the feature's one host synchronisation
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        triangles = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        if nv:
+            a.vertices, a.triangles = ctypes.c_void_p(vertices.data_ptr()), ctypes.c_void_p(triangles.data_ptr())
+            a.max_vertices, a.max_triangles = nv, nf
+            check(L.dgs_marching_cubes_emit(ctypes.byref(a), stream), "dgs_marching_cubes_emit")
+        if occ.is_cuda:
+            for t in (occ, ws, counts):
+                t.record_stream(torch.cuda.current_stream(dev))
+    return vertices, triangles
+
+
+def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None):
+    """gs_core.py:855-860 up to the marching cubes: extract_fields (sets pc.mesh_center / pc.mesh_scale), marching cubes at
+    density_thresh, vertices / (resolution - 1) * 2 - 1 -> Mesh on pc's device.  The reference's clean_mesh / decimate_mesh (pymeshlab)
+    are not part of this: hand them mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy()."""
+    occ = extract_fields(pc, resolution, num_blocks, lib=lib)
+    vertices, triangles = marching_cubes(occ, density_thresh, lib=lib)
+    return Mesh(vertices / (resolution - 1.0) * 2 - 1, triangles)
+
+
+def save_mesh_ply(path, vertices, faces):
+    """Binary little-endian PLY: element vertex (x y z float), element face (list uchar int vertex_indices), triangles only."""
+    n = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    v, f = n(vertices).astype("<f4", copy=False).reshape(-1, 3), n(faces).astype("<i4", copy=False).reshape(-1, 3)
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    el = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    el["n"], el["i"] = 3, f
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y",
+              "property float z", f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(np.ascontiguousarray(v).tobytes())
+        out.write(el.tobytes())
+
+
+def load_mesh_ply(path):
+    """-> (vertices float32 [V, 3], faces int32 [F, 3]) numpy arrays of a file written by save_mesh_ply (float x y z vertices, triangle
+    faces as `list uchar int`)."""
+    with open(path, "rb") as f:
+        assert f.readline().strip() == b"ply"
+        assert f.readline().split()[:2] == [b"format", b"binary_little_endian"], "only binary little-endian files (what save_mesh_ply writes)"
+        counts, props, cur = {}, {}, None
+        for line in iter(f.readline, b""):
+            tok = line.decode("ascii").split()
+            if tok[0] == "end_header":
+                break
+            if tok[0] == "element":
+                cur = tok[1]
+                counts[cur], props[cur] = int(tok[2]), []
+            elif tok[0] == "property":
+                props[cur].append(tok[1:])
+        assert list(counts) == ["vertex", "face"] and props["vertex"] == [["float", "x"], ["float", "y"], ["float", "z"]], props
+        assert props["face"] == [["list", "uchar", "int", "vertex_indices"]], props
+        v = np.frombuffer(f.read(12 * counts["vertex"]), dtype="<f4").reshape(-1, 3)
+        el = np.frombuffer(f.read(13 * counts["face"]), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+        assert v.shape[0] == counts["vertex"] and el.shape[0] == counts["face"] and bool((el["n"] == 3).all())
+        return v.astype(np.float32), np.ascontiguousarray(el["i"]).astype(np.int32)

@@ -45,7 +45,8 @@ class AttrDict(dict):
 
 class GaussianModel:
     """Container + activations of gs_core.py:321-373,544-570 (exp / normalize / sigmoid), the filters of :376-496 (torch expressions
-    on the raw parameters, in place, returning self) and the density field of :786-852 (csrc/field.hip)."""
+    on the raw parameters, in place, returning self), the density field of :786-852 (csrc/field.hip) and its
+    mesh, :855-860 (csrc/mesh.hip)."""
 
     def __init__(self, sh_degree, scaling_modifier=None):
         self.sh_degree, self.scaling_modifier = sh_degree, scaling_modifier
@@ -147,6 +148,12 @@ class GaussianModel:
         """gs_core.py:786-852 -> occ [R, R, R]; sets self.mesh_center / self.mesh_scale (dgs_amd/consumers.py, csrc/field.hip)."""
         from . import consumers
         return consumers.extract_fields(self, resolution, num_blocks, relax_ratio, lib)
+
+    def extract_mesh(self, density_thresh=0.005, resolution=256, num_blocks=64, lib=None):
+        """gs_core.py:855-860 -> consumers.Mesh(vertices [V, 3] in [-1, 1]^3, faces [F, 3]) on the model's device: extract_fields,
+        then marching cubes on the device (csrc/mesh.hip); sets self.mesh_center / self.mesh_scale as extract_fields does."""
+        from . import consumers
+        return consumers.extract_mesh(self, density_thresh, resolution, num_blocks, lib)
 
     # -- on-disk format, gs_core.py:578-760 (dgs_amd/consumers.py) --
     def construct_dtypes(self, use_fp16=False, enable_gs_viewer=True):
