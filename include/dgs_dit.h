@@ -146,7 +146,8 @@ typedef struct DgsDitAttentionBackwardArgs {
 int32_t dgs_dit_attention_backward_slots(int32_t L);
 
 typedef struct DgsDitLayerNormArgs {
-    int32_t rows, width;       /* width == 1024 (one wave per row, 16 elements per lane) or any multiple of 64 <= 2048 */
+    int32_t rows, width;       /* width in {256, 512, 768, 1024, 2048} (one wave per row, width / 64 elements per lane);
+                                  anything else is DGS_ERR_INVALID_ARGUMENT                            */
     const float* x;            /* f32 [rows, width]                                                   */
     const float* weight;       /* [width] or NULL                                                     */
     const float* shift;        /* [batch, mod_stride] or NULL -> no modulate                           */
@@ -158,8 +159,11 @@ typedef struct DgsDitLayerNormArgs {
     int32_t out_f32;
 } DgsDitLayerNormArgs;
 
-/* Backward of dgs_dit_layernorm: h = LN(x) * weight * (1 + scale) + shift.  dx_out = dx_in + dLN; column sums over the
- * rows of each sample are ADDED to dshift / dscale ([batch, mod_stride]) and dweight ([width]) with fp32 atomics. */
+/* Backward of dgs_dit_layernorm: h = LN(x) * weight * (1 + scale) + shift.  dx_out = dx_in + dLN (dx_out == dx_in is allowed).
+ * The column sums dshift / dscale ([batch, mod_stride], over the rows of each sample) and dweight ([width], over all rows) are
+ * WRITTEN, not accumulated: every workgroup writes its partial rows to the `scratch` slab, one ordered reduce sums them and stores
+ * the result (no atomics; columns of a [batch, mod_stride] row outside [0, width) are not touched).
+ * Limits: width in {256, 512, 1024}, anything else is DGS_ERR_INVALID_ARGUMENT; rows is a multiple of rows_per_batch (0 -> rows). */
 typedef struct DgsDitLayerNormBackwardArgs {
     int32_t rows, width;
     const float* x;            /* f32 [rows, width]: the forward's input                               */
@@ -178,8 +182,10 @@ typedef struct DgsDitLayerNormBackwardArgs {
     size_t scratch_bytes;
 } DgsDitLayerNormBackwardArgs;
 
-/* Backward of dgs_dit_rowlinear (M <= 8): dW [N,K], db [N] and dx [M,K] are WRITTEN (dx through per-workgroup partial rows in
- * `scratch`, summed in a fixed order). */
+/* Backward of dgs_dit_rowlinear: dW [N,K], db [N] and dx [M,K] are WRITTEN (dx through per-workgroup partial rows in
+ * `scratch`, summed in a fixed order).
+ * Limits: M <= 8, K % 8 == 0, K <= 1024 and 2 * MR * K * 4 <= 65536 bytes of LDS (MR = M rounded up to 1, 2, 4 or 8: both hold
+ * up to M = 8 with K = 1024); anything else is DGS_ERR_INVALID_ARGUMENT. */
 typedef struct DgsDitRowLinearBackwardArgs {
     int32_t M, N, K;
     const float* x;            /* f32 [M, K] forward input (before the optional SiLU)                  */
@@ -207,7 +213,8 @@ typedef struct DgsDitGateMulArgs {
 } DgsDitGateMulArgs;
 
 typedef struct DgsDitRowLinearArgs {
-    int32_t M, N, K;           /* M <= 16 rows; K % 512 == 0 or K == 256                              */
+    int32_t M, N, K;           /* M <= 16 rows; K % 512 == 0 or K == 256; MR * K * 4 <= 65536 bytes of LDS (MR = M rounded
+                                  up to 1, 2, 4, 8 or 16), else DGS_ERR_INVALID_ARGUMENT                */
     const float* x;            /* f32 [M, K]                                                          */
     int32_t silu_input;        /* 1: apply SiLU to x first (adaLN_modulation = Sequential(SiLU, Linear)) */
     const uint16_t* W;         /* bf16 [N, K]                                                         */

@@ -398,13 +398,15 @@ int launch_rowlinear(const DgsDitRowLinearArgs* a, hipStream_t st) {
     p.M = a->M; p.N = a->N; p.K = a->K; p.silu_in = a->silu_input; p.silu_out = a->silu_output;
     p.x = a->x; p.W = a->W; p.bias = a->bias; p.out = a->out;
     const dim3 grid((a->N + kRowLinFeatures - 1) / kRowLinFeatures), block(256);
-    if (a->M <= 1) hipLaunchKernelGGL((rowlinear_kernel<1>), grid, block, (size_t)1 * a->K * 4, st, p);
-    else if (a->M <= 2) hipLaunchKernelGGL((rowlinear_kernel<2>), grid, block, (size_t)2 * a->K * 4, st, p);
-    else if (a->M <= 4) hipLaunchKernelGGL((rowlinear_kernel<4>), grid, block, (size_t)4 * a->K * 4, st, p);
-    else if (a->M <= 8) hipLaunchKernelGGL((rowlinear_kernel<8>), grid, block, (size_t)8 * a->K * 4, st, p);
-    else {
-        if ((size_t)16 * a->K * 4 > 65536) return DGS_ERR_INVALID_ARGUMENT;
-        hipLaunchKernelGGL((rowlinear_kernel<16>), grid, block, (size_t)16 * a->K * 4, st, p);
+    const int mr = a->M <= 1 ? 1 : a->M <= 2 ? 2 : a->M <= 4 ? 4 : a->M <= 8 ? 8 : 16;
+    const size_t lds = (size_t)mr * a->K * sizeof(float);      // the MR staged rows of x
+    if (lds > 65536) return DGS_ERR_INVALID_ARGUMENT;          // refused here for every MR, not left to fail at launch
+    switch (mr) {
+        case 1: hipLaunchKernelGGL((rowlinear_kernel<1>), grid, block, lds, st, p); break;
+        case 2: hipLaunchKernelGGL((rowlinear_kernel<2>), grid, block, lds, st, p); break;
+        case 4: hipLaunchKernelGGL((rowlinear_kernel<4>), grid, block, lds, st, p); break;
+        case 8: hipLaunchKernelGGL((rowlinear_kernel<8>), grid, block, lds, st, p); break;
+        default: hipLaunchKernelGGL((rowlinear_kernel<16>), grid, block, lds, st, p); break;
     }
     return launch_ok();
 }
