@@ -337,6 +337,35 @@ int dgs_dit_backward(const DgsDitModel* m, const DgsDitModelT* mt, const DgsDitG
 int dgs_dit_gemm(const DgsDitGemmArgs* a, dgs_stream_t stream);
 int32_t dgs_dit_gemm_sliced_tile(const DgsDitGemmArgs* a);   /* diagnostic: tile width (256 / 192 / 128) if this call runs on the 256-row
                                                                  ring kernel (dit_gemm_deep.hip), 0 otherwise; launches nothing */
+/* What a dgs_dit_gemm call with these arguments runs on this device: the kernel family, its tile and how the work is cut.  Filled
+ * by the code that fills the launch parameters (the launchers stop in front of the launch), so it cannot drift from them. */
+typedef enum DgsGemmFamily {
+    DGS_GEMM_FAMILY_SIMPLE128 = 1,   /* dit_gemm.hip: 128 x 128|64 tiles, two LDS stages                                    */
+    DGS_GEMM_FAMILY_RING256 = 2,     /* dit_gemm_deep.hip: 256 x 256|192|128 tiles on the 4-stage ring, 8 or 4 waves         */
+    DGS_GEMM_FAMILY_RING128 = 3,     /* the ring on 128 x 128 tiles (two K groups)                                          */
+    DGS_GEMM_FAMILY_SPLITK = 4       /* the 256 x 256 ring kernel over K splits + the reduction kernel                      */
+} DgsGemmFamily;
+typedef enum DgsGemmTailForm {       /* the tile row of every sample that holds a single live 32-row block                  */
+    DGS_GEMM_TAIL_NONE = 0,          /* no such row in this launch (or, 128-wide kernel: it is an ordinary tile row)        */
+    DGS_GEMM_TAIL_GEMV = 1,          /* two-row GEMV items (<= 2 live rows)                                                 */
+    DGS_GEMM_TAIL_MFMA = 2,          /* single-block MFMA items                                                             */
+    DGS_GEMM_TAIL_RING_ROW = 3       /* the shape fits neither: the row runs the ring like a full tile row                  */
+} DgsGemmTailForm;
+typedef struct DgsDitGemmPlan {
+    int32_t family;                  /* DgsGemmFamily                                                                       */
+    int32_t bm, bn, waves;           /* tile rows, tile columns, waves per workgroup                                        */
+    int32_t full_items;              /* full-tile work items (split-K: tiles, each run nsplit times)                        */
+    int32_t tail_form;               /* DgsGemmTailForm                                                                     */
+    int32_t tail_items;              /* GEMV / MFMA items                                                                   */
+    int32_t tail_wgs;                /* > 0: that many workgroups behind the tiles run the items (idle CUs); 0 with items: the
+                                        first tile workgroups take them (128-wide kernel: always one workgroup per item)    */
+    int32_t map2d;                   /* ring: workgroup -> tile through 4 x 2 blocks of the tile grid per XCD                */
+    int32_t nsplit, splits_per_batch;/* split-K: partial planes, splits of one sample's K; 1, 1 elsewhere                   */
+    int32_t gemv_tail_rows;          /* 128-wide kernel: the last tile row's <= 2 live rows are GEMV items behind the tiles  */
+    int32_t grid;                    /* workgroups of the (first) launch                                                    */
+} DgsDitGemmPlan;
+/* diagnostic: launches nothing.  DGS_OK and *out filled, or the status dgs_dit_gemm would return without launching. */
+int32_t dgs_dit_gemm_plan(const DgsDitGemmArgs* a, DgsDitGemmPlan* out);
 int dgs_dit_attention(const DgsDitAttentionArgs* a, dgs_stream_t stream);
 int dgs_dit_attention_backward(const DgsDitAttentionBackwardArgs* a, dgs_stream_t stream);
 int dgs_dit_layernorm(const DgsDitLayerNormArgs* a, dgs_stream_t stream);

@@ -225,18 +225,18 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmParams p) {
 }
 
 int sliced_gemm_tile(int M, int N, int K, int epilogue, int k_per_batch, int rows_per_batch, int valid_rows);   // dit_gemm_deep.hip
-int launch_sliced_gemm(const GemmCore& c, int epilogue, int bn, hipStream_t st, bool quad, bool rows_external);
+int launch_sliced_gemm(const GemmCore& c, int epilogue, int bn, hipStream_t st, bool quad, bool rows_external, DgsDitGemmPlan* plan);
 bool sliced_rows_are_gemv(int K, int N, int valid_rows);
 bool sliced128_eligible(int M, int N, int K, int epilogue, int k_per_batch, int rows_per_batch);
 int splitk_plan(int M, int N, int K, int k_per_batch, int* splits_per_batch);
-int launch_splitk_gemm(const DgsDitGemmArgs* a, int k_per_batch, hipStream_t st);
+int launch_splitk_gemm(const DgsDitGemmArgs* a, int k_per_batch, hipStream_t st, DgsDitGemmPlan* plan);
 
 }  // namespace dgs
 
 using namespace dgs;
 
-template <int EPI>
-static void launch_gemm(const GemmCore& c, int k_per_batch, int bn, hipStream_t st) {
+// The work distribution of one launch of gemm_bf16_kernel<EPI, bn>: everything launch_gemm decides.
+static GemmParams plan_gemm(const GemmCore& c, int k_per_batch, int bn, bool qkv) {
     GemmParams p;
     static_cast<GemmCore&>(p) = c;
     p.k_per_batch = k_per_batch;
@@ -248,7 +248,7 @@ static void launch_gemm(const GemmCore& c, int k_per_batch, int bn, hipStream_t 
     static const int no_tail = getenv("DGS_GEMM_NO_GEMV_TAIL") ? atoi(getenv("DGS_GEMM_NO_GEMV_TAIL")) : 0;   // measurement aid
     p.ntail = 0; p.tail_row0 = 0;
     if (!no_tail && p.full_rows > 1 && last_live <= 2 && p.K % 512 == 0 && p.K <= 4096 && p.k_per_batch == p.K && p.N % 8 == 0 &&
-        !(EPI == DGS_EPI_QKV)) {
+        !qkv) {
         --p.full_rows;
         p.tail_row0 = p.full_rows * BM;
         p.ntail = (p.M / p.rows_per_batch) * (p.N / 8);
@@ -257,14 +257,31 @@ static void launch_gemm(const GemmCore& c, int k_per_batch, int bn, hipStream_t 
     p.ntiles = p.tiles_m * p.tiles_n;
     static const int map_env = getenv("DGS_GEMM_MAP") ? atoi(getenv("DGS_GEMM_MAP")) : 0;
     p.map_mode = map_env;
+    return p;
+}
+
+template <int EPI>
+static void launch_gemm(const GemmCore& c, int k_per_batch, int bn, hipStream_t st, DgsDitGemmPlan* plan) {
+    const GemmParams p = plan_gemm(c, k_per_batch, bn, EPI == DGS_EPI_QKV);
+    if (plan) {                                                   // dgs_dit_gemm_plan: nothing is launched
+        plan->family = DGS_GEMM_FAMILY_SIMPLE128;
+        plan->bm = BM; plan->bn = bn; plan->waves = 4;
+        plan->full_items = p.ntiles;
+        plan->tail_form = p.ntail > 0 ? DGS_GEMM_TAIL_GEMV : DGS_GEMM_TAIL_NONE;
+        plan->tail_items = p.ntail; plan->tail_wgs = 0; plan->map2d = 0; plan->nsplit = 1; plan->splits_per_batch = 1;
+        plan->gemv_tail_rows = p.ntail > 0 ? 1 : 0;
+        plan->grid = p.ntail + p.ntiles;
+        return;
+    }
     if (bn == 128) hipLaunchKernelGGL((gemm_bf16_kernel<EPI, 128>), dim3(p.ntail + p.ntiles), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((gemm_bf16_kernel<EPI, 64>), dim3(p.ntail + p.ntiles), dim3(256), 0, st, p);
 }
 
+// mode 4: no launch, `plan` receives what mode 0 would launch (dgs_dit_gemm_plan).
 // mode 3: no launch, the tile width of the sliced 256-row kernel this call runs on (256 / 192 / 128), 0 for the other kernels.
 // mode 0: dgs_dit_gemm.  mode 1: the same launch without the two-row GEMV side jobs of the sliced 256-row kernel (the caller
 // produces those rows: layernorm_rows_gemv_kernel); an error if the shape does not run there.  mode 2: no launch, 1 if mode 1 applies.
-static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode) {
+static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode, DgsDitGemmPlan* plan = nullptr) {
     if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->M % BM || a->N % 64 || a->K % BK) return DGS_ERR_INVALID_ARGUMENT;
     if (!a->A || !a->W || !a->out || (a->lda & 7) || (a->ldw & 7)) return DGS_ERR_INVALID_ARGUMENT;
     const int kpb = a->k_per_batch > 0 ? a->k_per_batch : a->K;
@@ -281,10 +298,10 @@ static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode)
     static const int env_algo = getenv("DGS_GEMM_ALGO") ? atoi(getenv("DGS_GEMM_ALGO")) : 0;
     const int algo = a->algo ? a->algo : env_algo;
     // weight-gradient shapes with a scratch buffer: split-K on the sliced kernel (any algo but an explicit SIMPLE128)
-    if (mode == 0 && (algo == DGS_GEMM_AUTO || algo == DGS_GEMM_SLICED) && a->splitk_ws && a->epilogue == DGS_EPI_F32 && !a->bias && a->ldo % 4 == 0 &&
+    if ((mode == 0 || mode == 4) && (algo == DGS_GEMM_AUTO || algo == DGS_GEMM_SLICED) && a->splitk_ws && a->epilogue == DGS_EPI_F32 && !a->bias && a->ldo % 4 == 0 &&
         p.rows_per_batch == a->M && p.valid_rows == a->M) {
         int spb = 0;
-        if (splitk_plan(a->M, a->N, a->K, kpb, &spb)) return launch_splitk_gemm(a, kpb, st0);
+        if (splitk_plan(a->M, a->N, a->K, kpb, &spb)) return launch_splitk_gemm(a, kpb, st0, plan);
     }
     // AUTO (measured on MI355X, tools/gemm_check.py; 128-wide kernel -> sliced kernel):
     //   1 sample  (M = 4352):  QKV 41 -> 39 us, fc1 + GELU 58 -> 44 us on 256 x 256 tiles (one round of the chip); the N = 1024
@@ -297,7 +314,7 @@ static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode)
         const int sbn = sliced_gemm_tile(a->M, a->N, a->K, a->epilogue, kpb, p.rows_per_batch, p.valid_rows);
         if (mode == 3) return sbn;
         if (mode == 2) return sbn && sliced_rows_are_gemv(a->K, a->N, p.valid_rows) && p.valid_rows < p.rows_per_batch ? 1 : 0;
-        if (sbn) return launch_sliced_gemm(p, a->epilogue, sbn, st0, algo == DGS_GEMM_QUAD, mode == 1);
+        if (sbn) return launch_sliced_gemm(p, a->epilogue, sbn, st0, algo == DGS_GEMM_QUAD, mode == 1, plan);
     }
     if (mode == 2 || mode == 3) return 0;
     if (mode == 1) return DGS_ERR_INVALID_ARGUMENT;
@@ -310,7 +327,7 @@ static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode)
     const bool few_tiles = (a->M / BM) * (a->N / 128) < 512 && a->N % 128 == 0;
     if ((algo == DGS_GEMM_SLICED128 || (algo == DGS_GEMM_AUTO && few_tiles && !no_s128 && a->K >= s128_mink)) &&
         sliced128_eligible(a->M, a->N, a->K, a->epilogue, kpb, p.rows_per_batch))
-        return launch_sliced_gemm(p, a->epilogue, -128, st0, false, false);
+        return launch_sliced_gemm(p, a->epilogue, -128, st0, false, false, plan);
     // 128 x 64 tiles when 128 x 128 would leave the 256 CUs with fewer than two workgroups each
     if (a->epilogue == DGS_EPI_QKV && a->N % 128) return DGS_ERR_INVALID_ARGUMENT;
     static const int env_bn = getenv("DGS_GEMM_BN") ? atoi(getenv("DGS_GEMM_BN")) : 0;      // measurement aid
@@ -319,17 +336,23 @@ static int gemm_dispatch(const DgsDitGemmArgs* a, dgs_stream_t stream, int mode)
     if (env_bn == 64) bn = 64;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (a->epilogue) {
-        case DGS_EPI_BF16: launch_gemm<DGS_EPI_BF16>(p, kpb, bn, st); break;
-        case DGS_EPI_GELU_BF16: launch_gemm<DGS_EPI_GELU_BF16>(p, kpb, bn, st); break;
-        case DGS_EPI_GATE_RESIDUAL: launch_gemm<DGS_EPI_GATE_RESIDUAL>(p, kpb, bn, st); break;
-        case DGS_EPI_F32: launch_gemm<DGS_EPI_F32>(p, kpb, bn, st); break;
-        case DGS_EPI_QKV: launch_gemm<DGS_EPI_QKV>(p, kpb, 128, st); break;
-        case DGS_EPI_DGELU_BF16: launch_gemm<DGS_EPI_DGELU_BF16>(p, kpb, bn, st); break;
+        case DGS_EPI_BF16: launch_gemm<DGS_EPI_BF16>(p, kpb, bn, st, plan); break;
+        case DGS_EPI_GELU_BF16: launch_gemm<DGS_EPI_GELU_BF16>(p, kpb, bn, st, plan); break;
+        case DGS_EPI_GATE_RESIDUAL: launch_gemm<DGS_EPI_GATE_RESIDUAL>(p, kpb, bn, st, plan); break;
+        case DGS_EPI_F32: launch_gemm<DGS_EPI_F32>(p, kpb, bn, st, plan); break;
+        case DGS_EPI_QKV: launch_gemm<DGS_EPI_QKV>(p, kpb, 128, st, plan); break;
+        case DGS_EPI_DGELU_BF16: launch_gemm<DGS_EPI_DGELU_BF16>(p, kpb, bn, st, plan); break;
         default: return DGS_ERR_INVALID_ARGUMENT;
     }
+    if (plan) return DGS_OK;
     return hipGetLastError() == hipSuccess ? DGS_OK : DGS_ERR_DEVICE;
 }
 
+extern "C" int32_t dgs_dit_gemm_plan(const DgsDitGemmArgs* a, DgsDitGemmPlan* out) {
+    if (!out) return DGS_ERR_INVALID_ARGUMENT;
+    *out = DgsDitGemmPlan{};
+    return gemm_dispatch(a, nullptr, 4, out);
+}
 extern "C" int dgs_dit_gemm(const DgsDitGemmArgs* a, dgs_stream_t stream) { return gemm_dispatch(a, stream, 0); }
 extern "C" int32_t dgs_dit_gemm_sliced_tile(const DgsDitGemmArgs* a) { const int w = gemm_dispatch(a, nullptr, 3); return w > 0 ? w : 0; }
 

@@ -500,9 +500,10 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
     }
 }
 
-template <int EPI, int BN, int NW = 8, int BM = 256>
-static int launch_sliced(DeepParams p, hipStream_t st) {
-    constexpr int LDS = (BM == 128 ? 8 : 4) * (BM * 32 * 2 + BN * 32 * 2);   // 128 KiB (256 x 256) / 96 KiB (256 x 128) / 128 KiB (128 x 128: 8 slabs, as 8 or 4 x 2)
+// The work distribution of one launch of gemm_sliced_kernel<EPI, BN, NW, EXP, BM>: everything launch_sliced decides before it touches
+// the device.  `ring_tail_row`: a tile row with a single live 32-row block that fits neither side-job form and runs the ring.
+static int plan_sliced(DeepParams& p, const int BM, const int BN, const int NW, bool* ring_tail_row) {
+    *ring_tail_row = false;
     p.tiles_n = p.N / BN;
     p.rows_ps = p.rows_per_batch / BM;
     p.full_rows = 0; p.tail_rows = 0;
@@ -515,6 +516,7 @@ static int launch_sliced(DeepParams p, hipStream_t st) {
     for (int i = 0; i < p.rows_ps; ++i) {                          // per sample: tile rows with >= 2 / exactly 1 live 32-row blocks
         const int live = (p.valid_rows - i * BM + 31) / 32;
         if (live > 1 || (live == 1 && !gemv_ok && !mfma_ok)) ++p.full_rows; else if (live == 1) ++p.tail_rows;
+        if (live == 1 && !gemv_ok && !mfma_ok) *ring_tail_row = true;
     }
     if (p.rows_external) {
         if (!gemv_ok || p.nsplit > 1) return DGS_ERR_INVALID_ARGUMENT;
@@ -528,7 +530,7 @@ static int launch_sliced(DeepParams p, hipStream_t st) {
     p.ntiles = p.nfull_items ? p.nfull_items : p.ntail;
     p.tail_wgs = 0;
     if (p.nsplit <= 1 && p.ntail > 0 && p.nfull_items > 0) {
-        static const int ncu = compute_unit_count();               // (the emulator reads DGS_EMU_CUS: tests exercise the tail-only workgroups with it)
+        const int ncu = compute_unit_count_cached();               // (the emulator reads DGS_EMU_CUS at every call: tests exercise the tail-only workgroups with it)
         const int idle = ncu - p.nfull_items;                      // a tile workgroup owns its CU's LDS
         if (idle > 0) p.tail_wgs = idle < p.ntail ? idle : p.ntail;
         p.ntiles += p.tail_wgs;
@@ -541,6 +543,28 @@ static int launch_sliced(DeepParams p, hipStream_t st) {
     const int rows_all = samples * p.full_rows;
     p.map2d = !no_map2d && BM == 256 && p.nsplit <= 1 && p.tail_wgs == 0 && rows_all % 4 == 0 && p.tiles_n % 2 == 0 && p.nfull_items % 8 == 0 &&
               p.nfull_items <= compute_unit_count_cached() ? 1 : 0;
+    return DGS_OK;
+}
+
+// dgs_dit_gemm_plan's view of a planned launch
+static void report_sliced(const DeepParams& p, int BM, int BN, int NW, bool ring_tail_row, DgsDitGemmPlan* plan) {
+    plan->family = p.nsplit > 1 ? DGS_GEMM_FAMILY_SPLITK : BM == 128 ? DGS_GEMM_FAMILY_RING128 : DGS_GEMM_FAMILY_RING256;
+    plan->bm = BM; plan->bn = BN; plan->waves = NW;
+    plan->full_items = p.nfull_items;
+    plan->tail_form = p.ntail > 0 ? (p.tail_mode == 2 ? DGS_GEMM_TAIL_GEMV : DGS_GEMM_TAIL_MFMA) : ring_tail_row ? DGS_GEMM_TAIL_RING_ROW : DGS_GEMM_TAIL_NONE;
+    plan->tail_items = p.ntail; plan->tail_wgs = p.tail_wgs; plan->map2d = p.map2d;
+    plan->nsplit = p.nsplit; plan->splits_per_batch = p.splits_per_batch;
+    plan->gemv_tail_rows = 0;
+    plan->grid = p.ntiles;
+}
+
+template <int EPI, int BN, int NW = 8, int BM = 256>
+static int launch_sliced(DeepParams p, hipStream_t st, DgsDitGemmPlan* plan) {
+    constexpr int LDS = (BM == 128 ? 8 : 4) * (BM * 32 * 2 + BN * 32 * 2);   // 128 KiB (256 x 256) / 96 KiB (256 x 128) / 128 KiB (128 x 128: 8 slabs, as 8 or 4 x 2)
+    bool ring_tail_row;
+    const int planned = plan_sliced(p, BM, BN, NW, &ring_tail_row);
+    if (planned != DGS_OK) return planned;
+    if (plan) { report_sliced(p, BM, BN, NW, ring_tail_row, plan); return DGS_OK; }    // dgs_dit_gemm_plan: nothing is launched
     auto kern = gemm_sliced_kernel<EPI, BN, NW, 0, BM>;
     if constexpr (kInstrumented && EPI == DGS_EPI_F32 && BN == 256 && BM == 256) {   // DGS_GEMM_EXP=1|2: the measurement variants (instrumented library only)
         static const int exp = getenv("DGS_GEMM_EXP") ? atoi(getenv("DGS_GEMM_EXP")) : 0;
@@ -627,15 +651,15 @@ bool sliced_rows_are_gemv(int K, int N, int valid_rows) {
     return last_live <= 2 && K >= 512 && K <= 4096 && (K & (K - 1)) == 0 && N % 64 == 0;
 }
 
-int launch_sliced_gemm(const GemmCore& c, int epilogue, int bn, hipStream_t st, bool quad, bool rows_external) {
+int launch_sliced_gemm(const GemmCore& c, int epilogue, int bn, hipStream_t st, bool quad, bool rows_external, DgsDitGemmPlan* plan) {
     DeepParams p;
     static_cast<GemmCore&>(p) = c;
     p.rows_external = rows_external ? 1 : 0;
     p.dbg = 0; p.nsplit = 1; p.splits_per_batch = 1; p.out_split_stride = 0;
     static const int s128_nw4 = getenv("DGS_GEMM_S128_NW4") ? atoi(getenv("DGS_GEMM_S128_NW4")) : 0;   // measurement aid: the 4-wave form of the 128 x 128 tile
-#define DGS_SLICED_CASE(E) case E: return bn == 256 ? (quad ? launch_sliced<E, 256, 4>(p, st) : launch_sliced<E, 256>(p, st)) : \
-                                   bn == 128 ? launch_sliced<E, 128>(p, st) : s128_nw4 ? launch_sliced<E, 128, 4, 128>(p, st) : launch_sliced<E, 128, 8, 128>(p, st)
-    if (bn == 192) return epilogue == DGS_EPI_QKV && !quad ? launch_sliced<DGS_EPI_QKV, 192>(p, st) : DGS_ERR_INVALID_ARGUMENT;
+#define DGS_SLICED_CASE(E) case E: return bn == 256 ? (quad ? launch_sliced<E, 256, 4>(p, st, plan) : launch_sliced<E, 256>(p, st, plan)) : \
+                                   bn == 128 ? launch_sliced<E, 128>(p, st, plan) : s128_nw4 ? launch_sliced<E, 128, 4, 128>(p, st, plan) : launch_sliced<E, 128, 8, 128>(p, st, plan)
+    if (bn == 192) return epilogue == DGS_EPI_QKV && !quad ? launch_sliced<DGS_EPI_QKV, 192>(p, st, plan) : DGS_ERR_INVALID_ARGUMENT;
     switch (epilogue) {
         DGS_SLICED_CASE(DGS_EPI_BF16);
         DGS_SLICED_CASE(DGS_EPI_GELU_BF16);
@@ -682,7 +706,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     *reinterpret_cast<float4*>(out + m * ldo + n) = acc;
 }
 
-int launch_splitk_gemm(const DgsDitGemmArgs* a, int k_per_batch, hipStream_t st) {
+int launch_splitk_gemm(const DgsDitGemmArgs* a, int k_per_batch, hipStream_t st, DgsDitGemmPlan* plan) {
     int spb = 1;
     const int nsplit = splitk_plan(a->M, a->N, a->K, k_per_batch, &spb);
     if (!nsplit || a->epilogue != DGS_EPI_F32 || a->bias || !a->splitk_ws || a->ldo % 4) return DGS_ERR_INVALID_ARGUMENT;
@@ -691,8 +715,8 @@ int launch_splitk_gemm(const DgsDitGemmArgs* a, int k_per_batch, hipStream_t st)
     // one "sample" of M rows whose reduction is one sample's K; the partial products go to the scratch planes, dense [M, N]
     p.K = k_per_batch; p.rows_per_batch = p.valid_rows = a->M; p.out = a->splitk_ws; p.ldo = a->N;
     p.dbg = 0; p.nsplit = nsplit; p.splits_per_batch = spb; p.out_split_stride = (long long)a->M * a->N; p.rows_external = 0;
-    const int rc = launch_sliced<DGS_EPI_F32, 256>(p, st);
-    if (rc != DGS_OK) return rc;
+    const int rc = launch_sliced<DGS_EPI_F32, 256>(p, st, plan);
+    if (rc != DGS_OK || plan) return rc;
     const size_t plane = (size_t)a->M * a->N;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((plane / 4 + 255) / 256)), dim3(256), 0, st, a->splitk_ws, static_cast<float*>(a->out), nsplit,
                        a->N, a->ldo, plane);

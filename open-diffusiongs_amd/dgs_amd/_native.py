@@ -160,6 +160,15 @@ class DgsDitGemmArgs(ctypes.Structure):
                 ("valid_rows", ctypes.c_int32), ("q_scale", ctypes.c_float), ("splitk_ws", ctypes.c_void_p)]
 
 
+GEMM_FAMILY_SIMPLE128, GEMM_FAMILY_RING256, GEMM_FAMILY_RING128, GEMM_FAMILY_SPLITK = 1, 2, 3, 4
+GEMM_TAIL_NONE, GEMM_TAIL_GEMV, GEMM_TAIL_MFMA, GEMM_TAIL_RING_ROW = 0, 1, 2, 3
+
+
+class DgsDitGemmPlan(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in ("family", "bm", "bn", "waves", "full_items", "tail_form", "tail_items", "tail_wgs", "map2d",
+                                                     "nsplit", "splits_per_batch", "gemv_tail_rows", "grid")]
+
+
 class DgsDitAttentionArgs(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("heads", ctypes.c_int32), ("L", ctypes.c_int32), ("lpad", ctypes.c_int32),
                 ("qk", ctypes.c_void_p), ("vt", ctypes.c_void_p), ("out", ctypes.c_void_p), ("scale", ctypes.c_float),
@@ -281,12 +290,15 @@ DIT_SYMBOLS = ["dgs_dit_gemm", "dgs_dit_attention", "dgs_dit_attention_backward"
                "dgs_dit_workspace_bytes", "dgs_dit_forward", "dgs_dit_gemm_splitk_bytes",
                "dgs_dit_attention_tail_bytes", "dgs_dit_run_blocks", "dgs_debug_poison_lds", "dgs_debug_clock_probe",
                "dgs_dit_layernorm_backward_scratch_bytes", "dgs_dit_rowlinear_backward_scratch_bytes", "dgs_dit_gate_mul_scratch_bytes",
-               "dgs_dit_workspace_bytes_for_tokens", "dgs_dit_attention_backward_slots", "dgs_dit_layernorm_gemm", "dgs_dit_layernorm_gemm_shares_rows", "dgs_dit_gemm_sliced_tile"]
+               "dgs_dit_workspace_bytes_for_tokens", "dgs_dit_attention_backward_slots", "dgs_dit_layernorm_gemm", "dgs_dit_layernorm_gemm_shares_rows", "dgs_dit_gemm_sliced_tile",
+               "dgs_dit_gemm_plan"]
 
 
 def _declare_dit(L):
     L.dgs_dit_gemm_sliced_tile.restype = ctypes.c_int32
     L.dgs_dit_gemm_sliced_tile.argtypes = [ctypes.POINTER(DgsDitGemmArgs)]
+    L.dgs_dit_gemm_plan.restype = ctypes.c_int32
+    L.dgs_dit_gemm_plan.argtypes = [ctypes.POINTER(DgsDitGemmArgs), ctypes.POINTER(DgsDitGemmPlan)]
     L.dgs_dit_layernorm_gemm_shares_rows.restype = ctypes.c_int32
     L.dgs_dit_layernorm_gemm_shares_rows.argtypes = [ctypes.POINTER(DgsDitLayerNormArgs), ctypes.POINTER(DgsDitGemmArgs)]
     L.dgs_dit_layernorm_gemm.restype = ctypes.c_int

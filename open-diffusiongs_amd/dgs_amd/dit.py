@@ -52,6 +52,26 @@ class DitOps:
              q_scale=0.0, splitk=False):
         """A bf16 [M,K], W bf16 [N,K] -> per epilogue (see dgs_dit.h).  `out` is required for GATE_RESIDUAL (in-place).
         splitk: hand the library its split-K scratch (weight-gradient shapes; a no-op where no split applies)."""
+        a, out, vt, _ws = self._gemm_args(A, W, bias, epilogue, out, gate, rows_per_batch, vt, valid_rows, resid, aux, shape, k_per_batch,
+                                          a_batch_stride, w_batch_stride, lda, ldw, algo, q_scale, splitk)
+        self.last_gemm_sliced_tile = int(self.lib.dgs_dit_gemm_sliced_tile(ctypes.byref(a)))
+        self._check(self.lib.dgs_dit_gemm(ctypes.byref(a), _stream(A.device)))
+        return (out, vt) if epilogue == _native.EPI_QKV else out
+
+    def gemm_plan(self, A, W, bias=None, epilogue=_native.EPI_BF16, out=None, gate=None, rows_per_batch=0, vt=None, valid_rows=0,
+                  resid=None, aux=None, shape=None, k_per_batch=0, a_batch_stride=0, w_batch_stride=0, lda=None, ldw=None, algo=0,
+                  q_scale=0.0, splitk=False):
+        """dgs_dit_gemm_plan: what `gemm` with the same arguments runs on this device (kernel family, tile, waves, how the last tile
+        row is handled, grid), as a dict of the DgsDitGemmPlan fields.  Launches nothing."""
+        a, _out, _vt, _ws = self._gemm_args(A, W, bias, epilogue, out, gate, rows_per_batch, vt, valid_rows, resid, aux, shape, k_per_batch,
+                                            a_batch_stride, w_batch_stride, lda, ldw, algo, q_scale, splitk)
+        plan = _native.DgsDitGemmPlan()
+        self._check(self.lib.dgs_dit_gemm_plan(ctypes.byref(a), ctypes.byref(plan)))
+        return {name: int(getattr(plan, name)) for name, _ in plan._fields_}
+
+    def _gemm_args(self, A, W, bias, epilogue, out, gate, rows_per_batch, vt, valid_rows, resid, aux, shape, k_per_batch,
+                   a_batch_stride, w_batch_stride, lda, ldw, algo, q_scale, splitk):
+        """DgsDitGemmArgs of `gemm` / `gemm_plan` with the outputs it allocates: (args, out, vt, split-K scratch)."""
         if shape is not None:          # batched-reduction form (weight gradients): operands are [batch, rows, tokens]
             M, N, K = shape
         else:
@@ -80,13 +100,12 @@ class DitOps:
         a.bias, a.epilogue, a.out, a.ldo = _p(bias), epilogue, _p(out), ldo
         a.gate, a.gate_stride, a.rows_per_batch, a.vt = _p(gate), (gate.stride(0) if gate is not None else 0), rows_per_batch, _p(vt)
         a.valid_rows, a.algo, a.q_scale = valid_rows, algo, q_scale
+        ws = None
         if splitk:
             nbytes = self.lib.dgs_dit_gemm_splitk_bytes(M, N, K, k_per_batch)
             ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=dev)
             a.splitk_ws = _p(ws) if nbytes else None
-        self.last_gemm_sliced_tile = int(self.lib.dgs_dit_gemm_sliced_tile(ctypes.byref(a)))
-        self._check(self.lib.dgs_dit_gemm(ctypes.byref(a), _stream(dev)))
-        return (out, vt) if epilogue == _native.EPI_QKV else out
+        return a, out, vt, ws
 
     def attention(self, qk, vt, L, heads, qkv_layout=False, lse2=None, q_prescaled=False, tail_mode=0, out=None):
         """qk bf16 [B*lpad, 2*heads*64], vt bf16 [B, heads*64, lpad] -> bf16 [B*lpad, heads*64].

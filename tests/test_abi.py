@@ -35,7 +35,7 @@ def test_every_declared_symbol_is_exported():
 
 
 def test_ctypes_structs_match_c_layout():
-    structs = ["DgsRasterForwardArgs", "DgsRasterBackwardArgs", "DgsDitGemmArgs", "DgsDitAttentionArgs", "DgsDitLayerNormArgs",
+    structs = ["DgsRasterForwardArgs", "DgsRasterBackwardArgs", "DgsDitGemmArgs", "DgsDitGemmPlan", "DgsDitAttentionArgs", "DgsDitLayerNormArgs",
                "DgsDitRowLinearArgs", "DgsDitLayerWeights", "DgsDitModel", "DgsDitForwardArgs", "DgsSamplerStepArgs", "DgsMseArgs",
                "DgsDitLayerNormBackwardArgs", "DgsDitRowLinearBackwardArgs", "DgsDitGateMulArgs", "DgsDitAttentionBackwardArgs",
                "DgsDitBackwardArgs", "DgsDitRunBlocksArgs", "DgsResizeArgs", "DgsAdamWTensor", "DgsAdamWArgs"]

@@ -93,7 +93,22 @@ def test_gemm_sliced_single_block_mfma_items(N):
     _check_single_block_mfma_items(DitOps(), DEV, N)
 
 
-@pytest.mark.parametrize("M,N,K", [(4224, 3072, 1024), (4224, 1024, 4096), (256, 896, 1024), (4224, 1024, 576)])
+# What dgs_dit_gemm_plan says each `algo` iteration of test_gemm_production_shapes runs (family, tile width, waves): M = 4224 is no
+# multiple of 256 and K = 576 none of 128, so SLICED / QUAD fall back to the 128-wide kernel there; (256, 896, 1024) runs the ring's
+# 256 x 128 tile (QUAD has no 4-wave form of it); M = 4352 is the eligible shape: 17 x 12 tiles of 256 x 256, 8 and 4 waves.
+_SIMPLE128, _RING = _native.GEMM_FAMILY_SIMPLE128, _native.GEMM_FAMILY_RING256
+_PRODUCTION_PLANS = {(4224, 3072, 1024): {1: (_SIMPLE128, 128, 4), 4: (_SIMPLE128, 128, 4), 5: (_SIMPLE128, 128, 4)},
+                     (4224, 1024, 4096): {1: (_SIMPLE128, 64, 4), 4: (_SIMPLE128, 64, 4), 5: (_SIMPLE128, 64, 4)},
+                     (256, 896, 1024): {1: (_SIMPLE128, 64, 4), 4: (_RING, 128, 8), 5: (_RING, 128, 8)},
+                     (4224, 1024, 576): {1: (_SIMPLE128, 64, 4), 4: (_SIMPLE128, 64, 4), 5: (_SIMPLE128, 64, 4)},
+                     (4352, 3072, 1024): {1: (_SIMPLE128, 128, 4), 4: (_RING, 256, 8), 5: (_RING, 256, 4)}}
+
+
+def _plan_key(plan):
+    return plan["family"], plan["bn"], plan["waves"]
+
+
+@pytest.mark.parametrize("M,N,K", [(4224, 3072, 1024), (4224, 1024, 4096), (256, 896, 1024), (4224, 1024, 576), (4352, 3072, 1024)])
 def test_gemm_production_shapes(M, N, K):
     g = torch.Generator(device=DEV).manual_seed(M + N + K)
     A = _bf(torch.randn(M, K, generator=g, device=DEV))
@@ -103,6 +118,8 @@ def test_gemm_production_shapes(M, N, K):
     ops = _ops()
     assert rel_l2(ops.gemm(A, W, bias, _native.EPI_F32), ref) < 1e-5
     for algo in (_native.GEMM_SIMPLE128, _native.GEMM_SLICED, _native.GEMM_QUAD):   # every kernel family (ineligible shapes fall back)
+        for epi in (_native.EPI_F32, _native.EPI_GELU_BF16):
+            assert _plan_key(ops.gemm_plan(A, W, bias, epi, algo=algo)) == _PRODUCTION_PLANS[M, N, K][algo], (algo, epi)
         assert rel_l2(ops.gemm(A, W, bias, _native.EPI_F32, algo=algo), ref) < 1e-5, algo
         assert rel_l2(ops.gemm(A, W, bias, _native.EPI_GELU_BF16, algo=algo).float(), F.gelu(ref, approximate="tanh")) < 4e-3, algo
     assert rel_l2(ops.gemm(A, W, bias, _native.EPI_BF16).float(), ref) < 4e-3
@@ -156,8 +173,20 @@ def test_block_gemms_at_the_shipped_shape_incl_learned_token_rows(name, N, K, ep
 @pytest.mark.parametrize("algo", [0, _native.GEMM_SLICED, _native.GEMM_QUAD])
 def test_gemm_training_epilogues_production_shapes(algo):
     """fc1 forward (GELU + saved pre-activation + transposed copy) and the fc2 input gradient (dGELU + transposed copy) at the
-    4-view token count, 2 samples with padding rows: values vs fp32 torch, transposed copies bit-equal to the row-major ones."""
-    B, rows, L, W = 2, 4224, 4098, 1024
+    4-view token count, 2 samples with padding rows: values vs fp32 torch, transposed copies bit-equal to the row-major ones.
+    4,224 rows per sample are no multiple of 256: every `algo` runs the 128-wide kernel here (asserted)."""
+    _training_epilogues(algo, 4224, (_SIMPLE128, 128, 4))
+
+
+@pytest.mark.parametrize("algo", [0, _native.GEMM_SLICED, _native.GEMM_QUAD])
+def test_gemm_training_epilogues_ring_eligible_shape(algo):
+    """The same with 4,352 rows per sample (the padding dgs_dit_lpad gives): 2 x 16 x 16 full tiles of 256 x 256 on the ring kernel, 8 waves
+    (AUTO: more than 8,192 rows; SLICED) or 4 (QUAD), the learned tokens' rows as GEMV side items."""
+    _training_epilogues(algo, 4352, (_RING, 256, 4 if algo == _native.GEMM_QUAD else 8))
+
+
+def _training_epilogues(algo, rows, plan_key):
+    B, L, W = 2, 4098, 1024
     g = torch.Generator(device=DEV).manual_seed(5)
     ops = _ops()
     x = _bf(torch.randn(B * rows, W, generator=g, device=DEV))
@@ -168,6 +197,7 @@ def test_gemm_training_epilogues_production_shapes(algo):
     tr = lambda t, n: t.reshape(B, rows, n).transpose(1, 2)
     vt = torch.zeros(B, 4 * W, rows, dtype=torch.bfloat16, device=DEV)
     aux = torch.zeros(B * rows, 4 * W, dtype=torch.bfloat16, device=DEV)
+    assert _plan_key(ops.gemm_plan(x, w1, b1, _native.EPI_GELU_BF16, rows_per_batch=rows, valid_rows=L, vt=vt, aux=aux, algo=algo)) == plan_key
     out = ops.gemm(x, w1, b1, _native.EPI_GELU_BF16, rows_per_batch=rows, valid_rows=L, vt=vt, aux=aux, algo=algo)
     assert rel_l2(aux.float()[live], u_ref[live]) < 4e-3
     assert rel_l2(out.float()[live], F.gelu(u_ref, approximate="tanh")[live]) < 4e-3
@@ -176,6 +206,7 @@ def test_gemm_training_epilogues_production_shapes(algo):
     w2t = _bf(torch.randn(4 * W, W, generator=g, device=DEV) * 0.03)          # K-contiguous copy of fc2.weight
     uu = aux.float().requires_grad_(True)
     F.gelu(uu, approximate="tanh").sum().backward()
+    assert _plan_key(ops.gemm_plan(dy, w2t, None, _native.EPI_DGELU_BF16, rows_per_batch=rows, valid_rows=L, vt=vt, aux=aux, algo=algo)) == plan_key
     du = ops.gemm(dy, w2t, None, _native.EPI_DGELU_BF16, rows_per_batch=rows, valid_rows=L, vt=vt, aux=aux, algo=algo)
     assert rel_l2(du.float()[live], ((dy.float() @ w2t.float().t()) * uu.grad)[live]) < 5e-3
     assert torch.equal(vt[:, :, :L], tr(du, 4 * W)[:, :, :L])

@@ -352,19 +352,23 @@ def test_gemm_split_k_weight_gradient(ops, monkeypatch):
 
 @pytest.mark.parametrize("N", [256, 128, -256])
 def test_gemm_sliced(ops, N):
-    """Sliced-schedule kernel (256 x 256|128 x 32 tiles, 4-stage LDS-DMA ring): several trips round the ring, the padding-row
-    path, and the QKV / gate-residual epilogues."""
+    """Sliced-schedule kernel on its 256 x 128 tile, 8 waves (dgs_dit_gemm_plan, asserted below: every id of this test runs that form --
+    sliced_gemm_tile gives the 256-wide tile from 160 tiles on, these shapes have 2 x 6 or 2 x 1 tiles of 256 x 128, and GEMM_QUAD has a
+    4-wave form of the 256-wide tile only): several trips round the ring, the padding-row path, and the QKV / gate-residual epilogues.
+    The true 256 x 256 kernels, 8 and 4 waves, run in test_dit_gemm_emu.py."""
     sl = _native.GEMM_SLICED
-    if N < 0:                                       # the 4-wave variant (128 x 128 per wave) of the 256 x 256 tile
+    if N < 0:                                       # asks for the 4-wave variant; at this tile count it gets the 8-wave 256 x 128 form
         sl, N = _native.GEMM_QUAD, -N
     g = torch.Generator().manual_seed(41 + N)
     M, K = 512, 1024                                # 32 K slabs = 8 trips round the ring; K % 1024 == 0: single-block tiles go direct
     if N == 256:
-        N = 768                                     # 2 x 3 tiles of 256 x 256: needs >= 160 tiles for AUTO, forced via algo here
+        N = 768                                     # 2 x 6 tiles of 256 x 128 (256-wide tiles need >= 160 of them, whatever `algo` says)
     A = _bf(torch.randn(M, K, generator=g))
     W = _bf(torch.randn(N, K, generator=g) * 0.2)
     bias = torch.randn(N, generator=g)
     ref = A.float() @ W.float().t() + bias
+    plan = ops.gemm_plan(A, W, bias, _native.EPI_F32, algo=sl)
+    assert (plan["family"], plan["bm"], plan["bn"], plan["waves"]) == (_native.GEMM_FAMILY_RING256, 256, 128, 8), plan
     out = ops.gemm(A, W, bias, _native.EPI_F32, algo=sl)
     assert torch.allclose(out, ref, atol=3e-3, rtol=1e-4)
     out = torch.full((M, N), 7.0)
