@@ -515,8 +515,31 @@ def _declare_mesh(L):
     return L
 
 
+class DgsMeshCleanArgs(ctypes.Structure):
+    _fields_ = [("V", ctypes.c_int64), ("F", ctypes.c_int64), ("vertices", ctypes.c_void_p), ("faces", ctypes.c_void_p),
+                ("min_faces", ctypes.c_int32), ("min_diag_pct", ctypes.c_double), ("counts", ctypes.c_void_p),
+                ("out_vertices", ctypes.c_void_p), ("out_faces", ctypes.c_void_p), ("labels", ctypes.c_void_p),
+                ("max_vertices", ctypes.c_int64), ("max_faces", ctypes.c_int64), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_int64)]
+
+
+# every symbol include/dgs_mesh_clean.h declares (checked by tests/test_mesh_clean.py)
+MESH_CLEAN_SYMBOLS = ["dgs_mesh_clean_count", "dgs_mesh_clean_emit", "dgs_mesh_clean_workspace_bytes"]
+
+
+def _declare_mesh_clean(L):
+    if not all(hasattr(L, name) for name in MESH_CLEAN_SYMBOLS):         # a build that predates the clean-up (an A/B side): consumers.py refuses it there
+        return L
+    for name in ("dgs_mesh_clean_count", "dgs_mesh_clean_emit"):
+        getattr(L, name).restype = ctypes.c_int
+        getattr(L, name).argtypes = [ctypes.POINTER(DgsMeshCleanArgs), ctypes.c_void_p]
+    L.dgs_mesh_clean_workspace_bytes.restype = ctypes.c_int64
+    L.dgs_mesh_clean_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    return L
+
+
 _declare_raster = _declare
 
 
-def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh prototypes on one library)
-    return _declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L))))))))
+def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up prototypes on one library)
+    return _declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L)))))))))

@@ -11,6 +11,8 @@ Mirrors diffusionGS/models/gsrenderer/gs_core.py:
                                                              synchronisation each; here one C call, csrc/field.hip)
     GaussianModel.extract_mesh                 :855-860     (reference: occ to the host, `mcubes.marching_cubes`; here two C calls on
                                                              the device grid, csrc/mesh.hip, and a two-integer readback between them)
+and of diffusionGS/utils/mesh_utils.py clean_mesh :119-125  (the two pymeshlab filters that remove small connected components; here
+                                                             remove_small_components, csrc/mesh_clean.hip, a five-integer readback)
 The reference writes / reads the file through the `plyfile` package (binary_little_endian 1.0, one "vertex" element, scalar
 properties in dtype order); that byte layout is restated here with numpy structured arrays -- no extra dependency.
 """
@@ -282,13 +284,75 @@ def marching_cubes(occ, level, lib=None):
     return vertices, triangles
 
 
-def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None):
+def remove_small_components(vertices, faces, min_f=64, min_d=20, return_labels=False, lib=None):
+    """The two floater filters of the reference's clean_mesh on the mesh's device (include/dgs_mesh_clean.h, csrc/mesh_clean.hip):
+    a connected component (faces sharing vertex indices) goes when it has fewer than min_f faces (0 = off) or when the diagonal of its
+    bounding box is below min_d percent of the mesh's (0 = off); vertices no kept face refers to go with it.  The defaults are the
+    reference's values.  vertices float32 [V, 3], faces int32 [F, 3] -> (vertices', faces') in input order, faces renumbered; with
+    return_labels also labels int32 [F], the smallest vertex index of each input face's component (-1: an index outside [0, V)).
+    dgs_mesh_clean_count, ONE readback of the five counts to size the outputs, dgs_mesh_clean_emit."""
+    from . import _native
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise ValueError(f"remove_small_components: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"remove_small_components: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+    if faces.device != vertices.device:
+        raise ValueError(f"remove_small_components: vertices on {vertices.device}, faces on {faces.device}")
+    if int(min_f) != min_f or min_f < 0 or not min_d >= 0:
+        raise ValueError(f"remove_small_components: min_f must be an integer >= 0 and min_d a percentage >= 0, got {min_f}, {min_d}")
+    with torch.no_grad():
+        vertices, faces = vertices.detach().contiguous(), faces.detach().contiguous()
+        dev = vertices.device
+        L = lib or _native.lib()
+        if not all(hasattr(L, name) for name in _native.MESH_CLEAN_SYMBOLS):
+            raise RuntimeError("remove_small_components: this build of the library predates the mesh clean-up -- rebuild it (`python -m dgs_amd.build`)")
+        a = _native.DgsMeshCleanArgs()
+        a.V, a.F = vertices.shape[0], faces.shape[0]
+        a.min_faces, a.min_diag_pct = int(min_f), float(min_d)
+        a.workspace_bytes = L.dgs_mesh_clean_workspace_bytes(a.V, a.F)
+        if a.workspace_bytes <= 0:
+            raise ValueError(f"remove_small_components: unsupported size V = {a.V}, F = {a.F} (at most 2^30 each)")
+        ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=dev)
+        counts = torch.empty(5, dtype=torch.int32, device=dev)              # the call writes uint32 [5]
+        a.counts, a.workspace = ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(ws.data_ptr())
+        a.vertices = ctypes.c_void_p(vertices.data_ptr()) if a.V else None
+        a.faces = ctypes.c_void_p(faces.data_ptr()) if a.F else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if vertices.is_cuda else None
+
+        def check(rc, name):
+            if rc != 0:
+                raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed: {rc} ({_native.status_string(L, rc)})")
+
+        check(L.dgs_mesh_clean_count(ctypes.byref(a), stream), "dgs_mesh_clean_count")
+        nv, nf = (c & 0xFFFFFFFF for c in counts.tolist()[:2])              # the feature's one host synchronisation
+        out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        out_f = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        labels = torch.empty(a.F, dtype=torch.int32, device=dev) if return_labels else None
+        if nf or (return_labels and a.F):
+            a.out_vertices = ctypes.c_void_p(out_v.data_ptr()) if nv else None
+            a.out_faces = ctypes.c_void_p(out_f.data_ptr()) if nf else None
+            a.labels = ctypes.c_void_p(labels.data_ptr()) if return_labels else None
+            a.max_vertices, a.max_faces = nv, nf
+            check(L.dgs_mesh_clean_emit(ctypes.byref(a), stream), "dgs_mesh_clean_emit")
+        if vertices.is_cuda:
+            for t in (vertices, faces, ws, counts):
+                t.record_stream(torch.cuda.current_stream(dev))
+    return (out_v, out_f, labels) if return_labels else (out_v, out_f)
+
+
+def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0):
     """gs_core.py:855-860 up to the marching cubes: extract_fields (sets pc.mesh_center / pc.mesh_scale), marching cubes at
-    density_thresh, vertices / (resolution - 1) * 2 - 1 -> Mesh on pc's device.  The reference's clean_mesh / decimate_mesh (pymeshlab)
-    are not part of this: hand them mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy()."""
+    density_thresh, vertices / (resolution - 1) * 2 - 1 -> Mesh on pc's device.  min_f / min_d > 0 then drop the floaters as the first two
+    filters of the reference's clean_mesh do (remove_small_components on the mesh in [-1, 1]^3, which is what clean_mesh sees; the
+    reference's values are min_f=64, min_d=20); with both 0, the default, the raw level set is returned and that path is not entered.
+    The rest of clean_mesh and decimate_mesh (pymeshlab) are not part of this: hand them mesh.vertices.cpu().numpy(),
+    mesh.faces.cpu().numpy() (INTEGRATION.md)."""
     occ = extract_fields(pc, resolution, num_blocks, lib=lib)
     vertices, triangles = marching_cubes(occ, density_thresh, lib=lib)
-    return Mesh(vertices / (resolution - 1.0) * 2 - 1, triangles)
+    vertices = vertices / (resolution - 1.0) * 2 - 1
+    if min_f or min_d:
+        vertices, triangles = remove_small_components(vertices, triangles, min_f=min_f, min_d=min_d, lib=lib)
+    return Mesh(vertices, triangles)
 
 
 def save_mesh_ply(path, vertices, faces):
