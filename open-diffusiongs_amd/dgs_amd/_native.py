@@ -538,8 +538,30 @@ def _declare_mesh_clean(L):
     return L
 
 
+class DgsMeshDecimateArgs(ctypes.Structure):
+    _fields_ = [("V", ctypes.c_int64), ("F", ctypes.c_int64), ("vertices", ctypes.c_void_p), ("faces", ctypes.c_void_p),
+                ("n", ctypes.c_int32), ("counts", ctypes.c_void_p), ("out_vertices", ctypes.c_void_p), ("out_faces", ctypes.c_void_p),
+                ("max_vertices", ctypes.c_int64), ("max_faces", ctypes.c_int64), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_int64)]
+
+
+# every symbol include/dgs_mesh_decimate.h declares (checked by tests/test_mesh_decimate.py)
+MESH_DECIMATE_SYMBOLS = ["dgs_mesh_decimate_count", "dgs_mesh_decimate_emit", "dgs_mesh_decimate_workspace_bytes"]
+
+
+def _declare_mesh_decimate(L):
+    if not all(hasattr(L, name) for name in MESH_DECIMATE_SYMBOLS):      # a build that predates the decimation (an A/B side): consumers.py refuses it there
+        return L
+    for name in ("dgs_mesh_decimate_count", "dgs_mesh_decimate_emit"):
+        getattr(L, name).restype = ctypes.c_int
+        getattr(L, name).argtypes = [ctypes.POINTER(DgsMeshDecimateArgs), ctypes.c_void_p]
+    L.dgs_mesh_decimate_workspace_bytes.restype = ctypes.c_int64
+    L.dgs_mesh_decimate_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]
+    return L
+
+
 _declare_raster = _declare
 
 
-def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up prototypes on one library)
-    return _declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L)))))))))
+def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up + decimation prototypes on one library)
+    return _declare_mesh_decimate(_declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L))))))))))

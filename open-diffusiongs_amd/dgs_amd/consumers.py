@@ -13,6 +13,9 @@ Mirrors diffusionGS/models/gsrenderer/gs_core.py:
                                                              the device grid, csrc/mesh.hip, and a two-integer readback between them)
 and of diffusionGS/utils/mesh_utils.py clean_mesh :119-125  (the two pymeshlab filters that remove small connected components; here
                                                              remove_small_components, csrc/mesh_clean.hip, a five-integer readback)
+                                   decimate_mesh :44-85     (pymeshlab's quadric edge collapse, order-dependent; here its commented
+                                                             alternative, vertex clustering, with an order-free definition:
+                                                             cluster_vertices / decimate_mesh, csrc/mesh_decimate.hip)
 The reference writes / reads the file through the `plyfile` package (binary_little_endian 1.0, one "vertex" element, scalar
 properties in dtype order); that byte layout is restated here with numpy structured arrays -- no extra dependency.
 """
@@ -340,18 +343,126 @@ def remove_small_components(vertices, faces, min_f=64, min_d=20, return_labels=F
     return (out_v, out_f, labels) if return_labels else (out_v, out_f)
 
 
-def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0):
-    """gs_core.py:855-860 up to the marching cubes: extract_fields (sets pc.mesh_center / pc.mesh_scale), marching cubes at
-    density_thresh, vertices / (resolution - 1) * 2 - 1 -> Mesh on pc's device.  min_f / min_d > 0 then drop the floaters as the first two
+class _Clustering:
+    """The mesh, the library and one workspace large enough for every n up to n_max: count(n) as often as the caller likes (one
+    readback of the five counts each), then emit() at the n counted last."""
+
+    def __init__(self, vertices, faces, n_max, lib, who):
+        from . import _native
+        if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+            raise ValueError(f"{who}: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+            raise ValueError(f"{who}: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+        if faces.device != vertices.device:
+            raise ValueError(f"{who}: vertices on {vertices.device}, faces on {faces.device}")
+        if int(n_max) != n_max or not 1 <= n_max <= 1024:
+            raise ValueError(f"{who}: the grid must have an integer number of cells per axis in [1, 1024], got {n_max}")
+        self.who, self._native = who, _native
+        self.vertices, self.faces = vertices.detach().contiguous(), faces.detach().contiguous()
+        self.dev = vertices.device
+        self.L = L = lib or _native.lib()
+        if not all(hasattr(L, name) for name in _native.MESH_DECIMATE_SYMBOLS):
+            raise RuntimeError(f"{who}: this build of the library predates the mesh decimation -- rebuild it (`python -m dgs_amd.build`)")
+        self.a = a = _native.DgsMeshDecimateArgs()
+        a.V, a.F = self.vertices.shape[0], self.faces.shape[0]
+        a.workspace_bytes = L.dgs_mesh_decimate_workspace_bytes(a.V, a.F, int(n_max))       # grows with n: enough for every n <= n_max
+        if a.workspace_bytes <= 0:
+            raise ValueError(f"{who}: unsupported size V = {a.V}, F = {a.F} (at most 2^30 each)")
+        self.ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=self.dev)
+        self.counts_dev = torch.empty(5, dtype=torch.int32, device=self.dev)  # the call writes uint32 [5]
+        a.counts, a.workspace = ctypes.c_void_p(self.counts_dev.data_ptr()), ctypes.c_void_p(self.ws.data_ptr())
+        a.vertices = ctypes.c_void_p(self.vertices.data_ptr()) if a.V else None
+        a.faces = ctypes.c_void_p(self.faces.data_ptr()) if a.F else None
+        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream) if vertices.is_cuda else None
+        self.counts = None
+
+    def _check(self, rc, name):
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed: {rc} ({self._native.status_string(self.L, rc)})")
+
+    def count(self, n):
+        """-> [V', F', degenerate, duplicates dropped, invalid] at n cells per axis; a host synchronisation."""
+        self.a.n = int(n)
+        self._check(self.L.dgs_mesh_decimate_count(ctypes.byref(self.a), self.stream), "dgs_mesh_decimate_count")
+        self.counts = [c & 0xFFFFFFFF for c in self.counts_dev.tolist()]
+        if self.counts[0] == 0xFFFFFFFF:
+            raise RuntimeError(f"{self.who}: dgs_mesh_decimate_count found no slot for a face in its table")
+        return self.counts
+
+    def emit(self):
+        nv, nf = self.counts[:2]
+        out_v = torch.empty((nv, 3), dtype=torch.float32, device=self.dev)
+        out_f = torch.empty((nf, 3), dtype=torch.int32, device=self.dev)
+        if nf:
+            a = self.a
+            a.out_vertices, a.out_faces = ctypes.c_void_p(out_v.data_ptr()), ctypes.c_void_p(out_f.data_ptr())
+            a.max_vertices, a.max_faces = nv, nf
+            self._check(self.L.dgs_mesh_decimate_emit(ctypes.byref(a), self.stream), "dgs_mesh_decimate_emit")
+        if self.vertices.is_cuda:
+            for t in (self.vertices, self.faces, self.ws, self.counts_dev):
+                t.record_stream(torch.cuda.current_stream(self.dev))
+        return out_v, out_f
+
+
+def cluster_vertices(vertices, faces, n, return_counts=False, lib=None):
+    """Vertex clustering on a uniform grid of n cells along the longest axis of the mesh's box, on the mesh's device
+    (include/dgs_mesh_decimate.h, csrc/mesh_decimate.hip; MeshLab's meshing_decimation_clustering with the null and duplicate faces
+    removed): the vertices of one cell become one vertex at their mean, faces with two corners in one cell go, of faces with the same
+    three cells the one of the smallest index stays; clusters no kept face refers to are not output.  vertices float32 [V, 3], faces
+    int32 [F, 3] -> (vertices' in ascending cell order, faces' in input order with their orientation); with return_counts also
+    [V', F', degenerate faces, duplicate faces dropped, invalid faces].  The same input gives the same bytes.  Clustering can leave
+    non-manifold edges where a thin part collapses.  dgs_mesh_decimate_count, ONE readback of the five counts,
+    dgs_mesh_decimate_emit."""
+    with torch.no_grad():
+        c = _Clustering(vertices, faces, n, lib, "cluster_vertices")
+        counts = c.count(n)
+        out_v, out_f = c.emit()
+    return (out_v, out_f, counts) if return_counts else (out_v, out_f)
+
+
+def decimate_mesh(vertices, faces, target, n_max=1024, return_n=False, lib=None):
+    """The counterpart of the reference's decimate_mesh(verts, faces, target) (mesh_utils.py:44-85) on the mesh's device, by vertex
+    clustering (cluster_vertices) instead of pymeshlab's quadric edge collapse.  If target <= 0 or F <= target the inputs come back
+    unchanged (the reference's own condition).  Otherwise the result has AT MOST `target` faces, at the grid size n this bisection
+    finds and nothing else: lo = 1, hi = n_max + 1; while hi - lo > 1: mid = (lo + hi) // 2, lo = mid if F'(mid) <= target else
+    hi = mid; n = lo.  F'(1) = 0, so F'(lo) <= target holds throughout.  F'(n) is not monotone in n, so n is not promised to be the
+    largest grid that meets the target.  At most 10 counts (dgs_mesh_decimate_count) with a readback of five integers each, then one
+    emit; the mesh never leaves the device.  With return_n also n (0 when the inputs came back)."""
+    if not target >= 0 and not target < 0:
+        raise ValueError(f"decimate_mesh: target must be a number, got {target}")
+    if target <= 0 or faces.shape[0] <= target:
+        return (vertices, faces, 0) if return_n else (vertices, faces)
+    with torch.no_grad():
+        c = _Clustering(vertices, faces, n_max, lib, "decimate_mesh")
+        lo, hi, last = 1, int(n_max) + 1, None
+        while hi - lo > 1:
+            mid = last = (lo + hi) // 2
+            if c.count(mid)[1] <= target:
+                lo = mid
+            else:
+                hi = mid
+        if last != lo:                                                     # the workspace holds another n's count
+            c.count(lo)
+        out_v, out_f = c.emit()
+    return (out_v, out_f, lo) if return_n else (out_v, out_f)
+
+
+def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0, decimate_target=0):
+    """gs_core.py:855-869: extract_fields (sets pc.mesh_center / pc.mesh_scale), marching cubes at density_thresh,
+    vertices / (resolution - 1) * 2 - 1 -> Mesh on pc's device.  min_f / min_d > 0 then drop the floaters as the first two
     filters of the reference's clean_mesh do (remove_small_components on the mesh in [-1, 1]^3, which is what clean_mesh sees; the
-    reference's values are min_f=64, min_d=20); with both 0, the default, the raw level set is returned and that path is not entered.
-    The rest of clean_mesh and decimate_mesh (pymeshlab) are not part of this: hand them mesh.vertices.cpu().numpy(),
-    mesh.faces.cpu().numpy() (INTEGRATION.md)."""
+    reference's values are min_f=64, min_d=20); with both 0, the default, that path is not entered.  decimate_target > 0 then brings
+    a mesh of more faces down to at most that many by vertex clustering on the device (decimate_mesh; the reference's value is 1e5,
+    by pymeshlab's quadric edge collapse); 0, the default, does not enter that path, and with all three 0 the raw level set is
+    returned.  The rest of clean_mesh (merging close vertices, non-manifold repair, remeshing: pymeshlab) is not part of this: hand it
+    mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy() (INTEGRATION.md)."""
     occ = extract_fields(pc, resolution, num_blocks, lib=lib)
     vertices, triangles = marching_cubes(occ, density_thresh, lib=lib)
     vertices = vertices / (resolution - 1.0) * 2 - 1
     if min_f or min_d:
         vertices, triangles = remove_small_components(vertices, triangles, min_f=min_f, min_d=min_d, lib=lib)
+    if decimate_target:
+        vertices, triangles = decimate_mesh(vertices, triangles, decimate_target, lib=lib)
     return Mesh(vertices, triangles)
 
 
