@@ -363,6 +363,7 @@ typedef struct DgsDitGemmPlan {
     int32_t nsplit, splits_per_batch;/* split-K: partial planes, splits of one sample's K; 1, 1 elsewhere                   */
     int32_t gemv_tail_rows;          /* 128-wide kernel: the last tile row's <= 2 live rows are GEMV items behind the tiles  */
     int32_t grid;                    /* workgroups of the (first) launch                                                    */
+    int32_t store_policy;            /* DGS_STORE_PLAIN or DGS_STORE_THROUGH: how the launch's row-major output leaves      */
 } DgsDitGemmPlan;
 /* diagnostic: launches nothing.  DGS_OK and *out filled, or the status dgs_dit_gemm would return without launching. */
 int32_t dgs_dit_gemm_plan(const DgsDitGemmArgs* a, DgsDitGemmPlan* out);
@@ -405,6 +406,15 @@ int dgs_dit_run_blocks(const DgsDitModel* m, const DgsDitRunBlocksArgs* a, dgs_s
  * asynchronously; a read that overtakes its DMA would otherwise see the previous launch's -- usually identical -- data and pass
  * unnoticed.  tests/ call it in front of the kernels under test. */
 int dgs_debug_poison_lds(dgs_stream_t stream);
+
+/* Store policy of the forward kernels' bulk outputs (GEMM epilogues, attention output, LayerNorm rows).  PLAIN: write-back stores,
+ * the output stays dirty in the L2s until the kernel ends.  THROUGH: agent-scope (sc1) stores, performed at the memory side while
+ * the epilogue runs.  AUTO: through for the kernel classes and grids where it measured faster, plain
+ * elsewhere.  The same values go to the same addresses under every policy.  The process starts with the environment variable
+ * DGS_STORE_POLICY=auto|plain|through (default auto, read once); this hook sets the policy for later launches of the process
+ * (tests, A/B tools) and returns DGS_ERR_INVALID_ARGUMENT for a value outside the enum. */
+typedef enum DgsStorePolicy { DGS_STORE_AUTO = 0, DGS_STORE_PLAIN = 1, DGS_STORE_THROUGH = 2 } DgsStorePolicy;
+int dgs_debug_store_policy(int32_t policy);
 
 /* Measurement hook (bench.py's `clock` object): 256 workgroups run a dependent fp32 chain for `microseconds` of the constant 100 MHz
  * clock (s_memrealtime); out (device int64[3]) receives {shader-clock cycles (s_memtime) workgroup 0 counted, 100 MHz ticks it

@@ -30,6 +30,7 @@
 
 #include "dit_common.h"
 #include "dgs_dit.h"
+#include "dit_kernels.h"
 
 namespace dgs {
 
@@ -41,6 +42,7 @@ constexpr float RESCALE_THR = 6.0f;          // deferred-max threshold in exp2 u
 
 struct AttnParams {
     int B, heads, L, lpad, ld_qk, k_offset, nqb, nfull, nmain, dbg, q_prescaled;
+    int store_through;       // store policy of the main epilogue's output stores (store16)
     int tail_r;              // tail queries THIS launch handles inside the main kernel: L % 32, or 0 when they run as a launch of their own (tail_mode)
     long long vt_batch_stride;
     float* lse2;
@@ -643,14 +645,14 @@ __global__ __launch_bounds__(512) void attention_fwd_kernel(AttnParams p) {
         for (int i = 0; i < 8; i += 2) {
             half_swap(outv[i].x, outv[i + 1].x);
             half_swap(outv[i].y, outv[i + 1].y);
-            *reinterpret_cast<uint4*>(orow + (i >> 2) * 32 + 8 * ((i & 3) + half)) = make_uint4(outv[i].x, outv[i].y, outv[i + 1].x, outv[i + 1].y);
+            store16(orow + (i >> 2) * 32 + 8 * ((i & 3) + half), make_uint4(outv[i].x, outv[i].y, outv[i + 1].x, outv[i + 1].y), p.store_through);
         }
     }
     MAIN_STAMP(4);
     if (!tail_r) return;
     // the last workgroup of this (sample, head) to get here merges the per-tile records
     // stores retire in order: with at most the 4 output stores outstanding, every record store of this wave has been
-    // performed (sc1: at the memory side).  A wave without live queries issued no output stores behind its records,
+    // performed (sc1: at the memory side; the hardware counter sees the output stores under either store policy).  A wave without live queries issued no output stores behind its records,
     // so it has to drain completely.
     if (wave_live) wait_vmcnt<4>();
     else wait_vmcnt<0>();
@@ -708,6 +710,7 @@ extern "C" int dgs_dit_attention(const DgsDitAttentionArgs* a, dgs_stream_t stre
     }
     p.qk = a->qk; p.vt = a->vt; p.out = a->out; p.q_prescaled = a->q_prescaled;
     p.scale_log2e = a->scale * 1.44269504088896341f;
+    p.store_through = store_through(STORE_ATTENTION, p.nmain <= compute_unit_count_cached());      // one workgroup per CU
     hipStream_t st = static_cast<hipStream_t>(stream);
     // 64 KiB of rings; DGS_ATTN_LDS_PAD (bytes) adds unused LDS to cap the workgroups per CU (measurement aid)
     static const int lds_pad = getenv("DGS_ATTN_LDS_PAD") ? atoi(getenv("DGS_ATTN_LDS_PAD")) : 0;

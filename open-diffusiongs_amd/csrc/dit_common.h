@@ -247,14 +247,67 @@ __device__ __forceinline__ void st_agent2(float* ptr, float a, float b) {
     asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(ptr), "v"(v) : "memory");
 #endif
 }
+// (s_nop: see st_agent_u4)
 __device__ __forceinline__ void st_agent4(float* ptr, float a, float b, float c, float d) {
 #ifdef HIPEMU
     ptr[0] = a; ptr[1] = b; ptr[2] = c; ptr[3] = d;
 #else
     typedef float f32x4_t __attribute__((ext_vector_type(4)));
     const f32x4_t v = {a, b, c, d};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(ptr), "v"(v) : "memory");
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(ptr), "v"(v) : "memory");
 #endif
+}
+// The same 16-byte store for a payload of four dwords (packed bf16, or fp32 bit patterns): what a kernel's bulk output takes under
+// the `through` store policy (store16 below).  Inline asm like st_agent4, not the raw-buffer-store builtin with the sc1 cache-policy
+// bit: that form is counted by the compiler, but it needs a buffer resource per output tensor (4 more SGPRs and 32-bit offsets) in
+// kernels that run at their register limits, and the form measured in tools/ubench/store_tail_bench.hip is this one.  No "memory"
+// clobber: the value arrives in registers, nothing in a kernel re-reads what it stores here, and a clobber would pin the epilogues'
+// LDS reads behind the store in front of them.  The uncounted entry only makes the compiler's own vmcnt waits stricter (see above).
+// The s_nop belongs to the store: a VMEM store of more than 8 bytes reads its data registers up to two cycles after it issues, and a
+// VALU write to them in that window corrupts what is stored.  hipcc's hazard recognizer pads its own stores; it does not look into an
+// asm statement, and it did schedule the next strip's v_cndmask onto the data register right behind this one (layernorm_rows_gemv_kernel
+// at width >= 1024: wrong LayerNorm rows under the through policy until the s_nop was here).
+__device__ __forceinline__ void st_agent_u4(void* ptr, uint4 v) {
+#ifdef HIPEMU
+    *reinterpret_cast<uint4*>(ptr) = v;
+#else
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    const u32x4_t d = {v.x, v.y, v.z, v.w};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(ptr), "v"(d));
+#endif
+}
+__device__ __forceinline__ void st_agent_u2(void* ptr, uint2 v) {      // 8 bytes: 2.7x the time per byte of the 16-byte form
+#ifdef HIPEMU
+    *reinterpret_cast<uint2*>(ptr) = v;
+#else
+    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+    const u32x2_t d = {v.x, v.y};
+    asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(ptr), "v"(d));
+#endif
+}
+// v, as a value the compiler cannot trace back: what is computed from it is computed behind this point
+__device__ __forceinline__ int opaque_late(int v) {
+#ifndef HIPEMU
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
+// the value lane ^ 1 holds (DPP quad_perm:[1,0,3,2], no LDS round trip)
+__device__ __forceinline__ uint32_t lane_xor1(uint32_t v) {
+#ifdef HIPEMU
+    return (uint32_t)__shfl_xor((int)v, 1);
+#else
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);
+#endif
+}
+// A kernel's bulk output store under its launch's store policy (`through`: wave-uniform, from the kernel parameters): plain leaves
+// the line dirty in the XCD's L2 until the kernel ends, through sends it to the memory side while the epilogue still runs.
+__device__ __forceinline__ void store16(void* ptr, uint4 v, int through) {
+    if (through) st_agent_u4(ptr, v);
+    else *reinterpret_cast<uint4*>(ptr) = v;
+}
+__device__ __forceinline__ void store16(void* ptr, float4 v, int through) {
+    store16(ptr, make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)), through);
 }
 __device__ __forceinline__ float2 ld_agent2(const float2* ptr) {
 #ifdef HIPEMU

@@ -64,12 +64,42 @@ __device__ __forceinline__ void ln_rows_role(const LnParams& p, int b, int local
     if (local >= p.rows_per_batch || row >= p.rows) return;
     float4 y[VPL];
     ln_row<VPL, WEIGHT, MOD>(p, b, row, lane, y);
+    if (!p.store_through) {                             // the stores as they always were
 #pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-        const int c4 = i * 64 + lane;
-        if constexpr (F32OUT) reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.width)[c4] = y[i];
-        else reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.out) + (size_t)row * p.width)[c4] =
-                 make_uint2(pack_bf2(y[i].x, y[i].y), pack_bf2(y[i].z, y[i].w));
+        for (int i = 0; i < VPL; ++i) {
+            const int c4 = i * 64 + lane;
+            if constexpr (F32OUT) reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.width)[c4] = y[i];
+            else reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.out) + (size_t)row * p.width)[c4] =
+                     make_uint2(pack_bf2(y[i].x, y[i].y), pack_bf2(y[i].z, y[i].w));
+        }
+        return;
+    }
+    // Store policy `through`.  The lane index is taken through opaque_late so that hipcc forms this branch's addresses HERE and not in
+    // front of ln_row's loads, where they cost the kernel a wave of occupancy (width 1024: 64 -> 65 VGPRs).
+    const int ll = opaque_late(lane);
+    if constexpr (F32OUT) {
+        float4* const orow = reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.width) + ll;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) store16(orow + i * 64, y[i], 1);
+        return;
+    }
+    // bf16: a lane's four values are 8 bytes, and 8-byte sc1 stores cost 2.7x the 16-byte ones per byte.  Lanes 2 k and 2 k + 1 hold
+    // neighbouring pieces of vectors i and i + 1: one exchange gives the even lane 16 contiguous bytes of vector i and the odd lane 16
+    // of vector i + 1 (a wave-instruction = two whole 512-byte segments of the row).  Same values, same addresses.
+    uint2* const orow = reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.out) + (size_t)row * p.width);
+    if constexpr (VPL % 2 == 0) {
+        const bool odd = ll & 1;
+        uint2* const mine = orow + (odd ? 64 + ll - 1 : ll);
+#pragma unroll
+        for (int i = 0; i < VPL; i += 2) {
+            const uint2 a = make_uint2(pack_bf2(y[i].x, y[i].y), pack_bf2(y[i].z, y[i].w));
+            const uint2 b = make_uint2(pack_bf2(y[i + 1].x, y[i + 1].y), pack_bf2(y[i + 1].z, y[i + 1].w));
+            const uint2 got = make_uint2(lane_xor1(odd ? a.x : b.x), lane_xor1(odd ? a.y : b.y));     // the neighbour's piece of MY vector
+            st_agent_u4(mine + i * 64, odd ? make_uint4(got.x, got.y, b.x, b.y) : make_uint4(a.x, a.y, got.x, got.y));
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) st_agent_u2(orow + i * 64 + ll, make_uint2(pack_bf2(y[i].x, y[i].y), pack_bf2(y[i].z, y[i].w)));
     }
 }
 
@@ -327,6 +357,8 @@ __global__ __launch_bounds__(256) void gaussians_kernel(GsParams p) {
 }
 
 static int launch_ok() { return hipGetLastError() == hipSuccess ? DGS_OK : DGS_ERR_DEVICE; }
+// a LayerNorm launch whose 256-thread workgroups are all resident at once (eight per CU)
+static bool ln_one_round(const dim3& grid) { return (long long)grid.x * grid.y <= 8LL * compute_unit_count_cached(); }
 
 int launch_layernorm(const DgsDitLayerNormArgs* a, hipStream_t st) {
     if (!a || a->rows <= 0 || !a->x || !a->out || a->width % 256 || a->width > 2048 || a->width <= 0) return DGS_ERR_INVALID_ARGUMENT;
@@ -336,6 +368,7 @@ int launch_layernorm(const DgsDitLayerNormArgs* a, hipStream_t st) {
     p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : a->rows;
     p.out_f32 = a->out_f32; p.eps = a->eps; p.x = a->x; p.weight = a->weight; p.shift = a->shift; p.scale = a->scale; p.out = a->out;
     const dim3 grid((p.rows_per_batch + 3) / 4, (a->rows + p.rows_per_batch - 1) / p.rows_per_batch), block(256);
+    p.store_through = store_through(STORE_LAYERNORM, ln_one_round(grid));
     const bool w = a->weight != nullptr, m = a->shift != nullptr, f = a->out_f32 != 0;
 #define DGS_LN_CASE(V)                                                                                                                   \
     case V:                                                                                                                              \
@@ -379,6 +412,7 @@ int launch_layernorm_rows_gemv(const DgsDitLayerNormArgs* a, const DgsDitGemmArg
     const int ks = a->width / 512 < 4 ? a->width / 512 : 4, cpi = 8 * (4 / ks);
     j.items = g->N / cpi;
     const dim3 grid(j.items + (p.rows_per_batch + 3) / 4, (a->rows + p.rows_per_batch - 1) / p.rows_per_batch), block(256);
+    p.store_through = store_through(STORE_LAYERNORM, ln_one_round(grid));
 #define DGS_LNG_CASE(V)                                                                                                                  \
     case V:                                                                                                                              \
         if (g->epilogue == DGS_EPI_QKV) hipLaunchKernelGGL((layernorm_rows_gemv_kernel<V, DGS_EPI_QKV>), grid, block, 0, st, p, j);       \

@@ -5,6 +5,8 @@
 // proj GEMM (+gate*y+residual) -> LN+modulate -> fc1 GEMM (+GELU) -> fc2 GEMM (+gate*y+residual): 7 launches, and the
 // adaLN modulation vectors of ALL blocks and both heads come from one weight-streaming GEMV up front (the
 // conditioning vector is the same for every block).
+#include <string.h>
+
 #include "dit_kernels.h"
 #include "raster_state.h"
 
@@ -77,6 +79,33 @@ __global__ __launch_bounds__(256) void clock_probe_kernel(long long* out, int ti
     const long long c1 = cycle_stamp();
     if (blockIdx.x == 0 && threadIdx.x == 0) { out[0] = c1 - c0; out[1] = w1 - w0; }
     if (x == 123.456f) out[2] = 1;                                     // keeps the chain
+}
+
+// ---- store policy (dit_kernels.h).  The mode is process-wide; launchers read it when they fill their parameters. ----
+static int& store_policy_mode() {
+    static int mode = [] {
+        const char* e = getenv("DGS_STORE_POLICY");
+        if (e && !strcmp(e, "plain")) return (int)DGS_STORE_PLAIN;
+        if (e && !strcmp(e, "through")) return (int)DGS_STORE_THROUGH;
+        if (e && *e && strcmp(e, "auto")) fprintf(stderr, "[dgs] DGS_STORE_POLICY=%s: not auto|plain|through, using auto\n", e);
+        return (int)DGS_STORE_AUTO;
+    }();
+    return mode;
+}
+// auto: through exactly for the classes whose own A/B against the parent commit's library won at one-round grids
+// (profiles/store_policy_ab.txt).  Multi-round grids spread their stores over the launch already and stay plain.
+constexpr bool kAutoThrough[6] = {
+    /* STORE_GEMM_QKV   */ false,
+    /* STORE_GEMM_GELU  */ true,
+    /* STORE_GEMM_GATE  */ true,
+    /* STORE_GEMM_OTHER */ false,
+    /* STORE_ATTENTION  */ false,
+    /* STORE_LAYERNORM  */ false,
+};
+int store_through(StoreClass cls, bool one_round) {
+    const int mode = store_policy_mode();
+    if (mode != DGS_STORE_AUTO) return mode == DGS_STORE_THROUGH ? 1 : 0;
+    return one_round && kAutoThrough[cls] ? 1 : 0;
 }
 
 static int token_count(const DgsDitModel* m, int V, int H, int W) { return m->n_gaussians + V * (H / m->patch) * (W / m->patch); }
@@ -185,6 +214,12 @@ extern "C" int dgs_debug_poison_lds(dgs_stream_t stream) {
     if (!ok) return DGS_ERR_DEVICE;
     hipLaunchKernelGGL(dgs::poison_lds_kernel, dim3(2048), dim3(256), kBytes, static_cast<hipStream_t>(stream), kBytes / 4);
     return hipGetLastError() == hipSuccess ? DGS_OK : DGS_ERR_DEVICE;
+}
+
+extern "C" int dgs_debug_store_policy(int32_t policy) {
+    if (policy != DGS_STORE_AUTO && policy != DGS_STORE_PLAIN && policy != DGS_STORE_THROUGH) return DGS_ERR_INVALID_ARGUMENT;
+    dgs::store_policy_mode() = policy;
+    return DGS_OK;
 }
 
 extern "C" int dgs_debug_clock_probe(int64_t* out, int32_t microseconds, dgs_stream_t stream) {

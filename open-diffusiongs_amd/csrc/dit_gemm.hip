@@ -236,7 +236,8 @@ int launch_splitk_gemm(const DgsDitGemmArgs* a, int k_per_batch, hipStream_t st,
 using namespace dgs;
 
 // The work distribution of one launch of gemm_bf16_kernel<EPI, bn>: everything launch_gemm decides.
-static GemmParams plan_gemm(const GemmCore& c, int k_per_batch, int bn, bool qkv) {
+static GemmParams plan_gemm(const GemmCore& c, int k_per_batch, int bn, int epilogue) {
+    const bool qkv = epilogue == DGS_EPI_QKV;
     GemmParams p;
     static_cast<GemmCore&>(p) = c;
     p.k_per_batch = k_per_batch;
@@ -257,12 +258,14 @@ static GemmParams plan_gemm(const GemmCore& c, int k_per_batch, int bn, bool qkv
     p.ntiles = p.tiles_m * p.tiles_n;
     static const int map_env = getenv("DGS_GEMM_MAP") ? atoi(getenv("DGS_GEMM_MAP")) : 0;
     p.map_mode = map_env;
+    // two workgroups per CU (48 KiB of LDS each): one round while the grid fits twice the chip
+    p.store_through = store_through(gemm_store_class(epilogue, c), p.ntail + p.ntiles <= 2 * compute_unit_count_cached());
     return p;
 }
 
 template <int EPI>
 static void launch_gemm(const GemmCore& c, int k_per_batch, int bn, hipStream_t st, DgsDitGemmPlan* plan) {
-    const GemmParams p = plan_gemm(c, k_per_batch, bn, EPI == DGS_EPI_QKV);
+    const GemmParams p = plan_gemm(c, k_per_batch, bn, EPI);
     if (plan) {                                                   // dgs_dit_gemm_plan: nothing is launched
         plan->family = DGS_GEMM_FAMILY_SIMPLE128;
         plan->bm = BM; plan->bn = bn; plan->waves = 4;
@@ -271,6 +274,7 @@ static void launch_gemm(const GemmCore& c, int k_per_batch, int bn, hipStream_t 
         plan->tail_items = p.ntail; plan->tail_wgs = 0; plan->map2d = 0; plan->nsplit = 1; plan->splits_per_batch = 1;
         plan->gemv_tail_rows = p.ntail > 0 ? 1 : 0;
         plan->grid = p.ntail + p.ntiles;
+        plan->store_policy = p.store_through ? DGS_STORE_THROUGH : DGS_STORE_PLAIN;
         return;
     }
     if (bn == 128) hipLaunchKernelGGL((gemm_bf16_kernel<EPI, 128>), dim3(p.ntail + p.ntiles), dim3(256), 0, st, p);

@@ -502,7 +502,7 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256) void gemm_sliced_kernel(DeepPa
 
 // The work distribution of one launch of gemm_sliced_kernel<EPI, BN, NW, EXP, BM>: everything launch_sliced decides before it touches
 // the device.  `ring_tail_row`: a tile row with a single live 32-row block that fits neither side-job form and runs the ring.
-static int plan_sliced(DeepParams& p, const int BM, const int BN, const int NW, bool* ring_tail_row) {
+static int plan_sliced(DeepParams& p, const int BM, const int BN, const int NW, const int epilogue, bool* ring_tail_row) {
     *ring_tail_row = false;
     p.tiles_n = p.N / BN;
     p.rows_ps = p.rows_per_batch / BM;
@@ -543,6 +543,8 @@ static int plan_sliced(DeepParams& p, const int BM, const int BN, const int NW, 
     const int rows_all = samples * p.full_rows;
     p.map2d = !no_map2d && BM == 256 && p.nsplit <= 1 && p.tail_wgs == 0 && rows_all % 4 == 0 && p.tiles_n % 2 == 0 && p.nfull_items % 8 == 0 &&
               p.nfull_items <= compute_unit_count_cached() ? 1 : 0;
+    // one workgroup per CU (96-128 KiB of LDS); the split-K partial planes (weight gradients) stay plain
+    p.store_through = p.nsplit <= 1 && store_through(gemm_store_class(epilogue, p), p.ntiles <= compute_unit_count_cached());
     return DGS_OK;
 }
 
@@ -556,13 +558,14 @@ static void report_sliced(const DeepParams& p, int BM, int BN, int NW, bool ring
     plan->nsplit = p.nsplit; plan->splits_per_batch = p.splits_per_batch;
     plan->gemv_tail_rows = 0;
     plan->grid = p.ntiles;
+    plan->store_policy = p.store_through ? DGS_STORE_THROUGH : DGS_STORE_PLAIN;
 }
 
 template <int EPI, int BN, int NW = 8, int BM = 256>
 static int launch_sliced(DeepParams p, hipStream_t st, DgsDitGemmPlan* plan) {
     constexpr int LDS = (BM == 128 ? 8 : 4) * (BM * 32 * 2 + BN * 32 * 2);   // 128 KiB (256 x 256) / 96 KiB (256 x 128) / 128 KiB (128 x 128: 8 slabs, as 8 or 4 x 2)
     bool ring_tail_row;
-    const int planned = plan_sliced(p, BM, BN, NW, &ring_tail_row);
+    const int planned = plan_sliced(p, BM, BN, NW, EPI, &ring_tail_row);
     if (planned != DGS_OK) return planned;
     if (plan) { report_sliced(p, BM, BN, NW, ring_tail_row, plan); return DGS_OK; }    // dgs_dit_gemm_plan: nothing is launched
     auto kern = gemm_sliced_kernel<EPI, BN, NW, 0, BM>;

@@ -65,6 +65,12 @@ constexpr int epi_strip_bytes(int nb) { return 32 * (32 * nb + 4) * 4; }     // 
 // acc[0 .. NB): NB side-by-side 32 x 32 accumulator blocks: rows m0 .. m0+31 (m0 = first row of the block), columns
 // n0 .. n0 + 32 NB - 1.  `patch` = this wave's private LDS patch (epi_strip_bytes(NB) bytes); nobody else touches it, so no
 // barrier is needed -- LDS operations of one wave execute in order.
+// Store policy (p.store_through, dit_kernels.h): the row-major pass of `out` -- F32, GATE_RESIDUAL, BF16, GELU_BF16, DGELU_BF16 and the
+// Q | K part of QKV: 16 bytes per lane, whole 64- to 256-byte row segments per wave-instruction -- goes through store16.  Plain
+// whatever the policy: the V^T octets and the transposed `vt` copies (store_token_octet: 32 contiguous bytes per feature and
+// instruction, partial lines that the L2 merges into whole ones before they leave; written through, every piece would be a fabric
+// write of its own), `aux` (training only), the scalar tail_store of the GEMV items (2- and 4-byte stores: 6-12x the time per byte as
+// sc1 stores) and store_block (a handful of single-block side items).
 // `pre`: the strip's residual values (GATE_RESIDUAL), loaded by the caller ahead of time in the layout of the row-major pass
 // below (pre[it] = row it * RPI + rr, columns cc .. cc + 3; 4 NB of them): residual_prefetch.
 template <int NB, class P>
@@ -123,11 +129,10 @@ __device__ __forceinline__ void store_strip_impl(const P& p, const f32x16* acc, 
             if (EPI == DGS_EPI_GATE_RESIDUAL) {
                 float4 x;
                 if constexpr (HAVE_PRE) x = pre[it]; else x = *reinterpret_cast<const float4*>(p.resid + o);
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + o) =
-                    make_float4(x.x + gate.x * v.x, x.y + gate.y * v.y, x.z + gate.z * v.z, x.w + gate.w * v.w);
+                store16(reinterpret_cast<float*>(p.out) + o, make_float4(x.x + gate.x * v.x, x.y + gate.y * v.y, x.z + gate.z * v.z, x.w + gate.w * v.w), p.store_through);
                 if (p.aux) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.aux) + o) = make_uint2(pack_bf2(v.x, v.y), pack_bf2(v.z, v.w));
             } else {
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + o) = v;
+                store16(reinterpret_cast<float*>(p.out) + o, v, p.store_through);
             }
         }
     } else {
@@ -153,8 +158,8 @@ __device__ __forceinline__ void store_strip_impl(const P& p, const f32x16* acc, 
                 v1 = make_float4(v1.x * epi_dgelu_tanh(__uint_as_float(ax.z << 16)), v1.y * epi_dgelu_tanh(__uint_as_float(ax.z & 0xffff0000u)),
                                  v1.z * epi_dgelu_tanh(__uint_as_float(ax.w << 16)), v1.w * epi_dgelu_tanh(__uint_as_float(ax.w & 0xffff0000u)));
             }
-            *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out) + o) =
-                make_uint4(pack_bf2(v0.x, v0.y), pack_bf2(v0.z, v0.w), pack_bf2(v1.x, v1.y), pack_bf2(v1.z, v1.w));
+            store16(reinterpret_cast<bf16_t*>(p.out) + o, make_uint4(pack_bf2(v0.x, v0.y), pack_bf2(v0.z, v0.w), pack_bf2(v1.x, v1.y), pack_bf2(v1.z, v1.w)),
+                    p.store_through);
             if (transposed && EPI != DGS_EPI_BF16) {
                 *reinterpret_cast<float4*>(st + row * S + cc) = v0;
                 *reinterpret_cast<float4*>(st + row * S + cc + 4) = v1;

@@ -5,8 +5,18 @@
 
 namespace dgs {
 
+// ---- store policy of the forward kernels' bulk outputs: plain stores leave a launch's whole output dirty in
+//      the L2s when the kernel ends, and the dependent launch behind it waits for the write-back; `through` (sc1) stores are performed
+//      at the memory side while the epilogue runs.  The same values go to the same addresses either way.  A launcher asks
+//      store_through(cls, one_round) when it fills its kernel's parameters; the answer rides there as a wave-uniform int. ----
+enum StoreClass { STORE_GEMM_QKV, STORE_GEMM_GELU, STORE_GEMM_GATE, STORE_GEMM_OTHER, STORE_ATTENTION, STORE_LAYERNORM };
+// `one_round`: every workgroup of the launch is resident at once, so all of them store in the launch's last microseconds (the B = 1
+// forward).  DGS_STORE_POLICY=auto|plain|through (read once) or dgs_debug_store_policy select the mode; auto: see dit_forward.hip.
+int store_through(StoreClass cls, bool one_round);
+
 struct LnParams {
     int rows, width, mod_stride, rows_per_batch, out_f32;
+    int store_through;       // store policy of the row stores (store16)
     float eps;
     const float *x, *weight, *shift, *scale;
     void* out;
@@ -47,6 +57,7 @@ struct GemmCore {
     bf16_t* vt;                      // transposed bf16 copy [batch, N, rows_per_batch] (QKV: V only)
     void* aux;                       // GELU: u out; GATE_RESIDUAL: y out; DGELU: u in   (bf16 [M, ldo])
     float q_scale;                   // QKV: factor on the q features
+    int store_through;               // store policy of store_strip's row-major pass (plan_gemm / plan_sliced decide; 0 elsewhere)
 };
 
 // The one place where the defaults of DgsDitGemmArgs are applied.
@@ -59,7 +70,16 @@ inline GemmCore gemm_core(const DgsDitGemmArgs* a) {
     c.A = a->A; c.W = a->W; c.bias = a->bias; c.out = a->out; c.gate = a->gate; c.vt = a->vt; c.aux = a->aux;
     c.resid = a->resid ? a->resid : static_cast<const float*>(a->out);
     c.q_scale = a->q_scale != 0.0f ? a->q_scale : 1.0f;
+    c.store_through = 0;
     return c;
+}
+
+// The store class of a GEMM call: the three inference epilogues of a DiT block; everything else -- F32, BF16, and every call that
+// also writes `aux` or a transposed `vt` copy, i.e. the training forms -- is OTHER.
+inline StoreClass gemm_store_class(int epilogue, const GemmCore& c) {
+    if (epilogue == DGS_EPI_QKV) return STORE_GEMM_QKV;
+    if (c.aux || c.vt) return STORE_GEMM_OTHER;
+    return epilogue == DGS_EPI_GELU_BF16 ? STORE_GEMM_GELU : epilogue == DGS_EPI_GATE_RESIDUAL ? STORE_GEMM_GATE : STORE_GEMM_OTHER;
 }
 
 // Second role of a LayerNorm + modulate launch: the consumer GEMM's output rows [row0, row0 + nrows) of every sample (nrows <= 2: the

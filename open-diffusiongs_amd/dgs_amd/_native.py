@@ -162,11 +162,12 @@ class DgsDitGemmArgs(ctypes.Structure):
 
 GEMM_FAMILY_SIMPLE128, GEMM_FAMILY_RING256, GEMM_FAMILY_RING128, GEMM_FAMILY_SPLITK = 1, 2, 3, 4
 GEMM_TAIL_NONE, GEMM_TAIL_GEMV, GEMM_TAIL_MFMA, GEMM_TAIL_RING_ROW = 0, 1, 2, 3
+STORE_AUTO, STORE_PLAIN, STORE_THROUGH = 0, 1, 2      # DgsStorePolicy
 
 
 class DgsDitGemmPlan(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int32) for name in ("family", "bm", "bn", "waves", "full_items", "tail_form", "tail_items", "tail_wgs", "map2d",
-                                                     "nsplit", "splits_per_batch", "gemv_tail_rows", "grid")]
+                                                     "nsplit", "splits_per_batch", "gemv_tail_rows", "grid", "store_policy")]
 
 
 class DgsDitAttentionArgs(ctypes.Structure):
@@ -288,7 +289,7 @@ DIT_SYMBOLS = ["dgs_dit_gemm", "dgs_dit_attention", "dgs_dit_attention_backward"
                "dgs_dit_rowlinear_backward", "dgs_dit_gate_mul", "dgs_dit_saved_bytes", "dgs_dit_backward_workspace_bytes",
                "dgs_dit_forward_train", "dgs_dit_backward", "dgs_dit_layernorm", "dgs_dit_rowlinear", "dgs_dit_lpad",
                "dgs_dit_workspace_bytes", "dgs_dit_forward", "dgs_dit_gemm_splitk_bytes",
-               "dgs_dit_attention_tail_bytes", "dgs_dit_run_blocks", "dgs_debug_poison_lds", "dgs_debug_clock_probe",
+               "dgs_dit_attention_tail_bytes", "dgs_dit_run_blocks", "dgs_debug_poison_lds", "dgs_debug_clock_probe", "dgs_debug_store_policy",
                "dgs_dit_layernorm_backward_scratch_bytes", "dgs_dit_rowlinear_backward_scratch_bytes", "dgs_dit_gate_mul_scratch_bytes",
                "dgs_dit_workspace_bytes_for_tokens", "dgs_dit_attention_backward_slots", "dgs_dit_layernorm_gemm", "dgs_dit_layernorm_gemm_shares_rows", "dgs_dit_gemm_sliced_tile",
                "dgs_dit_gemm_plan"]
@@ -330,6 +331,9 @@ def _declare_dit(L):
         fn.restype = ctypes.c_size_t
         fn.argtypes = [ctypes.POINTER(DgsDitModel), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     L.dgs_dit_saved_bytes.argtypes = L.dgs_dit_saved_bytes.argtypes + [ctypes.c_int32]
+    if hasattr(L, "dgs_debug_store_policy"):              # the A/B tools also load the parent commit's library, which has none
+        L.dgs_debug_store_policy.restype = ctypes.c_int
+        L.dgs_debug_store_policy.argtypes = [ctypes.c_int32]
     L.dgs_debug_poison_lds.restype = ctypes.c_int
     L.dgs_debug_poison_lds.argtypes = [ctypes.c_void_p]
     L.dgs_debug_clock_probe.restype = ctypes.c_int

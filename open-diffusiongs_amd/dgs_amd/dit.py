@@ -39,6 +39,11 @@ class DitOps:
         LDS-DMA cannot pass on the previous launch's data."""
         self._check(self.lib.dgs_debug_poison_lds(ctypes.c_void_p(torch.cuda.current_stream(torch.device(device)).cuda_stream)))
 
+    def store_policy(self, policy):
+        """Test / A-B hook (dgs_debug_store_policy): _native.STORE_AUTO | STORE_PLAIN | STORE_THROUGH for the bulk output stores of
+        every later forward-kernel launch of the process."""
+        self._check(self.lib.dgs_debug_store_policy(int(policy)))
+
     def shader_clock_mhz(self, device="cuda:0", microseconds=20):
         """Measurement hook (dgs_debug_clock_probe): the effective shader clock where the stream stands, from the two hardware
         counters (s_memtime: shader clock, s_memrealtime: constant 100 MHz).  Synchronises."""

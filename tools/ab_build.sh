@@ -1,14 +1,26 @@
 #!/bin/bash
-# Builds open-diffusiongs_amd/lib/libdgs_hip_base.so = the product library with ONE csrc file taken from a git revision (default
-# HEAD) instead of the working tree: the "A" of an A/B run on the GPU box (tools/attn_ab.py takes both libraries in one process;
-# *.so is git-ignored but travels with gpurun).
-#   tools/ab_build.sh dit_attention.hip [rev]      then   gpurun -- 'python tools/attn_ab.py open-diffusiongs_amd/lib/libdgs_hip_base.so'
+# Builds open-diffusiongs_amd/lib/libdgs_hip_base.so = the "A" of an A/B run on the GPU box (tools/attn_ab.py, gemm_ab.py, ln_ab.py and
+# ab_bench.py take both libraries; *.so is git-ignored):
+#   tools/ab_build.sh dit_attention.hip [rev]   the product library with ONE csrc file taken from a git revision (default HEAD)
+#                                               instead of the working tree
+#   tools/ab_build.sh all [rev]                 the whole library of that revision, built in a second checkout (a change that
+#                                               touches shared headers or several files)
+#   then, on the GPU:   python tools/attn_ab.py open-diffusiongs_amd/lib/libdgs_hip_base.so
 set -eu
 f=$1; rev=${2:-HEAD}
 R=$(cd "$(dirname "$0")/.." && pwd)
 L=$R/open-diffusiongs_amd/lib
-PYTHONPATH=$R/open-diffusiongs_amd python -m dgs_amd.build > /dev/null          # objects of the working tree
 tmp=$(mktemp -d)
+if [ "$f" = all ]; then
+    mkdir -p "$L"
+    git -C "$R" archive "$rev" open-diffusiongs_amd/csrc open-diffusiongs_amd/dgs_amd include | tar -x -C "$tmp"
+    (cd "$tmp" && PYTHONPATH=$tmp/open-diffusiongs_amd python -c "from dgs_amd import build; build.build_hip()") > /dev/null
+    cp "$tmp/open-diffusiongs_amd/lib/libdgs_hip.so" "$L/libdgs_hip_base.so"
+    rm -rf "$tmp"
+    echo "$L/libdgs_hip_base.so  (whole library from $rev)"
+    exit 0
+fi
+PYTHONPATH=$R/open-diffusiongs_amd python -m dgs_amd.build > /dev/null          # objects of the working tree
 git -C "$R" show "$rev:open-diffusiongs_amd/csrc/$f" > "$tmp/$f"
 extra=$(python - "$f" <<'PY'
 import sys

@@ -44,18 +44,27 @@ for L, B in ((4098, 1), (4130, 1), (290, 2), (18, 2), (1026, 1), (600, 1), (1638
     print(f"L={L} B={B}: outputs bit-identical: {same}; finite: {bool(torch.isfinite(vb.float()).all())}; "
           f"max |diff| {float((va.float() - vb.float()).abs().max()):.3g}{tail}", flush=True)
 
-for L, B, n in ((4098, 1, 60), (4098, 4, 20), (16386, 1, 8)):
+ROUNDS = 7
+for L, B, n in ((4098, 1, 40), (4098, 4, 12), (16386, 1, 6)):
+    # per round: n alternating launches of base, base again and new; a new / base ratio means something only against the spread of the
+    # base / base ratios of the same run
     qk, vt, lpad = case(L, B)
-    ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)] for k in ("base", "new")}
+    runs = (("base", base), ("base2", base), ("new", new))
     for _ in range(5):
         base.attention(qk, vt, L, heads, q_prescaled=True); new.attention(qk, vt, L, heads, q_prescaled=True)
-    for i in range(n):
-        for k, ops in (("base", base), ("new", new)):
-            e0, e1 = ev[k][i]
-            e0.record(); ops.attention(qk, vt, L, heads, q_prescaled=True); e1.record()
-    torch.cuda.synchronize()
-    t = {k: sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in v) for k, v in ev.items()}
-    med = {k: v[len(v) // 2] for k, v in t.items()}
+    bb, nb, med = [], [], {}
+    for _ in range(ROUNDS):
+        ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)] for k, _ in runs}
+        for i in range(n):
+            for k, ops in runs:
+                e0, e1 = ev[k][i]
+                e0.record(); ops.attention(qk, vt, L, heads, q_prescaled=True); e1.record()
+        torch.cuda.synchronize()
+        med = {k: sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in v)[n // 2] for k, v in ev.items()}
+        bb.append(med["base2"] / med["base"]); nb.append(med["new"] / med["base"])
     flops = 4.0 * L * L * W * B
-    print(f"timing L={L} B={B}: base {med['base']:.1f} us ({flops / med['base'] / 1e6:.0f} TFLOP/s)  new {med['new']:.1f} us "
-          f"({flops / med['new'] / 1e6:.0f} TFLOP/s)  ratio {med['new'] / med['base']:.3f}  (median of {n}, incl. the output memset)", flush=True)
+    print(f"timing L={L} B={B}: last round base {med['base']:.1f} us ({flops / med['base'] / 1e6:.0f} TFLOP/s)  new {med['new']:.1f} us "
+          f"({flops / med['new'] / 1e6:.0f} TFLOP/s)  (median of {n}, incl. the output memset)\n"
+          f"    base / base per round " + " ".join(f"{r:.3f}" for r in bb) + "\n    new  / base per round " + " ".join(f"{r:.3f}" for r in nb) +
+          f"\n    new / base median {sorted(nb)[ROUNDS // 2]:.3f}; base / base spread [{min(bb):.3f}, {max(bb):.3f}]: "
+          f"{'all below' if max(nb) < min(bb) else 'all above' if min(nb) > max(bb) else 'overlaps'}", flush=True)

@@ -29,17 +29,26 @@ for B, rows, kind in ((1, 4352, "mod"), (4, 4352, "mod"), (1, 4352, "weight_f32"
     a, b = call(ops[0]), call(ops[1])
     torch.cuda.synchronize()
     print(f"B={B} rows={rows} {kind}: outputs bit-identical: {torch.equal(a, b)}; finite {bool(torch.isfinite(b.float()).all())}", flush=True)
-    n, reps = 30, 8
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)] for _ in ops]
-    for i in range(n):
-        for k, o in enumerate(ops):
-            e0, e1 = ev[k][i]
-            e0.record()
-            for _ in range(reps):
-                call(o)
-            e1.record()
-    torch.cuda.synchronize()
-    med = [sorted(e0.elapsed_time(e1) * 1e3 / reps for e0, e1 in v)[n // 2] for v in ev]
+    # per round: n alternating timed groups of base, base again and new; a new / base ratio means something only against the spread of
+    # the base / base ratios of the same run
+    n, reps, rounds = 20, 8, 7
+    runs = (ops[0], ops[0], ops[1])
+    bb, nb, med = [], [], []
+    for _ in range(rounds):
+        ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)] for _ in runs]
+        for i in range(n):
+            for k, o in enumerate(runs):
+                e0, e1 = ev[k][i]
+                e0.record()
+                for _ in range(reps):
+                    call(o)
+                e1.record()
+        torch.cuda.synchronize()
+        med = [sorted(e0.elapsed_time(e1) * 1e3 / reps for e0, e1 in v)[n // 2] for v in ev]
+        bb.append(med[1] / med[0]); nb.append(med[2] / med[0])
     nbytes = M * W * (8.0 if kind != "mod" else 6.0)
-    print(f"timing B={B} rows={rows} {kind}: base {med[0]:.2f} us ({nbytes / med[0] / 1e6:.2f} TB/s)  new {med[1]:.2f} us ({nbytes / med[1] / 1e6:.2f} TB/s)  "
-          f"ratio {med[1] / med[0]:.3f}  (per launch, {reps} back to back incl. the output allocation)", flush=True)
+    print(f"timing B={B} rows={rows} {kind}: last round base {med[0]:.2f} us ({nbytes / med[0] / 1e6:.2f} TB/s)  new {med[2]:.2f} us ({nbytes / med[2] / 1e6:.2f} TB/s)  "
+          f"(per launch, {reps} back to back incl. the output allocation)\n    base / base per round " + " ".join(f"{r:.3f}" for r in bb) +
+          "\n    new  / base per round " + " ".join(f"{r:.3f}" for r in nb) +
+          f"\n    new / base median {sorted(nb)[rounds // 2]:.3f}; base / base spread [{min(bb):.3f}, {max(bb):.3f}]: "
+          f"{'all below' if max(nb) < min(bb) else 'all above' if min(nb) > max(bb) else 'overlaps'}", flush=True)
