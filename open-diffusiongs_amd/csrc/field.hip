@@ -1,7 +1,7 @@
 // field.hip -- the Gaussian density field on a voxel grid (include/dgs_field.h DgsFieldArgs; the reference's
 // GaussianModel.extract_fields, diffusionGS/models/gsrenderer/gs_core.py:786-852, a host loop over num_blocks^3 blocks).
 //
-// Five launches and one memset per call, all on the caller's stream:
+// Five launches and one memset per call, all on the caller's stream (the first four live in field_cells.h, shared with mesh_attr.hip):
 //   field_key_kernel      thread = Gaussian: the coarse cell (pitch block_size = 2 / nb) of its normalised centre, counted per cell
 //   field_scan_kernel     one workgroup: exclusive scan of the nb^3 counts -> cell offsets; the counts become the scatter's cursors
 //   field_scatter_kernel  thread = Gaussian: its index into its cell's segment, at whatever slot the atomic hands out
@@ -48,111 +48,13 @@
 
 #include "dgs_device.h"
 #include "dgs_field.h"
+#include "field_cells.h"     // FieldWs, field_cell, the key / scan / scatter / prepare kernels, field_exp
 
 namespace dgs {
 
-constexpr int FIELD_WG = 256;
 constexpr int FIELD_VPT = 4;         // voxels per thread and pass when split > 4
 constexpr int FIELD_ZB = 4;          // z-adjacent blocks per workgroup when split <= 4
-constexpr int FIELD_MAX_NB = 256, FIELD_MAX_R = 2048;
-
-struct FieldWs {
-    uint32_t *count, *offsets, *keys, *index;
-    float4* rec;
-    int64_t bytes;
-    __host__ FieldWs(void* base, int64_t N, int64_t nb) {
-        const int64_t cells = nb * nb * nb;
-        auto up = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
-        char* p = static_cast<char*>(base);
-        int64_t at = 0;
-        count = reinterpret_cast<uint32_t*>(p + at);   at += up(4 * cells);
-        offsets = reinterpret_cast<uint32_t*>(p + at); at += up(4 * (cells + 1));
-        keys = reinterpret_cast<uint32_t*>(p + at);    at += up(4 * N);
-        index = reinterpret_cast<uint32_t*>(p + at);   at += up(4 * N);
-        rec = reinterpret_cast<float4*>(p + at);       at += 48 * N;
-        bytes = at;
-    }
-};
-
-// Cell of a coordinate on the grid of pitch 2 / nb over [-1, 1], clamped; every step is monotone in x, so lo < x < hi implies
-// field_cell(lo) <= field_cell(x) <= field_cell(hi).  A NaN lands in cell 0 (and is a member of nothing).
-__device__ __forceinline__ int field_cell(float x, int nb) {
-    const float t = floorf((x + 1.0f) * (0.5f * (float)nb));
-    if (!(t >= 0.f)) return 0;
-    if (t > (float)(nb - 1)) return nb - 1;
-    return (int)t;
-}
-
-__global__ __launch_bounds__(FIELD_WG) void field_key_kernel(DgsFieldArgs a, FieldWs ws) {
-    const int i = blockIdx.x * FIELD_WG + threadIdx.x;
-    if (i >= a.N) return;
-    const int cx = field_cell(a.xyz[3 * (size_t)i], a.nb), cy = field_cell(a.xyz[3 * (size_t)i + 1], a.nb), cz = field_cell(a.xyz[3 * (size_t)i + 2], a.nb);
-    const uint32_t key = ((uint32_t)cx * a.nb + cy) * a.nb + cz;
-    ws.keys[i] = key;
-    atomicAdd(&ws.count[key], 1u);                       // a count: the same whatever the arrival order
-}
-
-__global__ __launch_bounds__(1024) void field_scan_kernel(FieldWs ws, int64_t cells) {
-    __shared__ uint32_t scratch[1024 / DGS_WAVE + 1];
-    const int64_t per = (cells + 1023) / 1024, c0 = per * threadIdx.x, c1 = c0 + per < cells ? c0 + per : cells;
-    uint32_t sum = 0;
-    for (int64_t c = c0; c < c1; ++c) sum += ws.count[c];
-    uint32_t total;
-    uint32_t run = block_exclusive_scan<1024>(sum, scratch, &total);
-    for (int64_t c = c0; c < c1; ++c) {
-        const uint32_t n = ws.count[c];
-        ws.offsets[c] = run;
-        ws.count[c] = 0;
-        run += n;
-    }
-    if (threadIdx.x == 0) ws.offsets[cells] = total;
-}
-
-__global__ __launch_bounds__(FIELD_WG) void field_scatter_kernel(DgsFieldArgs a, FieldWs ws) {
-    const int i = blockIdx.x * FIELD_WG + threadIdx.x;
-    if (i >= a.N) return;
-    const uint32_t key = ws.keys[i];
-    ws.index[ws.offsets[key] + atomicAdd(&ws.count[key], 1u)] = (uint32_t)i;
-}
-
-__global__ __launch_bounds__(FIELD_WG) void field_prepare_kernel(DgsFieldArgs a, FieldWs ws) {
-    const int i = blockIdx.x * FIELD_WG + threadIdx.x;
-    if (i >= a.N) return;
-    const uint32_t key = ws.keys[i], beg = ws.offsets[key], end = ws.offsets[key + 1];
-    uint32_t rank = 0;
-    for (uint32_t j = beg; j < end; ++j) rank += ws.index[j] < (uint32_t)i ? 1u : 0u;
-    // -1/2 Sigma^-1 = -1/2 R diag(1 / s^2) R^T, s = exp(scaling) * scaling_modifier * mesh_scale, R of the normalised quaternion
-    const double mul = (double)a.scaling_modifier * (double)a.mesh_scale;
-    double w[3];
-    for (int k = 0; k < 3; ++k) {
-        const double s = exp((double)a.scaling[3 * (size_t)i + k]) * mul;
-        w[k] = -0.5 / (s * s);
-    }
-    double q[4];
-    for (int k = 0; k < 4; ++k) q[k] = (double)a.rotation[4 * (size_t)i + k];
-    const double inv = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const double r = q[0] * inv, x = q[1] * inv, y = q[2] * inv, z = q[3] * inv;
-    const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)},
-                            {2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x)},
-                            {2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)}};
-    auto m = [&](int p, int q2) { return R[p][0] * R[q2][0] * w[0] + R[p][1] * R[q2][1] * w[1] + R[p][2] * R[q2][2] * w[2]; };
-    const double op = 1.0 / (1.0 + exp(-(double)a.opacity[i]));
-    // power = A dx^2 + D dy^2 + F dz^2 + B dx dy + C dx dz + E dy dz: the off-diagonal coefficients carry the factor 2
-    float4* out = ws.rec + 3 * (size_t)(beg + rank);
-    out[0] = make_float4(a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2], (float)op);
-    out[1] = make_float4((float)m(0, 0), (float)(2 * m(0, 1)), (float)(2 * m(0, 2)), (float)m(1, 1));
-    out[2] = make_float4((float)(2 * m(1, 2)), (float)m(2, 2), 0.f, 0.f);
-}
-
-__device__ __forceinline__ float field_exp(float power) {
-    const float kL2eHi = 1.44269504088896341f;
-    const float kL2eLo = (float)(1.44269504088896341 - (double)1.44269504088896341f);
-    const float t = power * kL2eHi;
-    float e = __builtin_fmaf(power, kL2eHi, -t);
-    e = __builtin_fmaf(power, kL2eLo, e);
-    const float ex = hw_exp2(t);
-    return __builtin_fmaf(ex, e * 0.693147180559945309f, ex);
-}
+constexpr int FIELD_MAX_R = 2048;
 
 // WAVE_PER_BLOCK: grid (ceil(nb / 4), nb, nb), wave w owns block (blockIdx.z, blockIdx.y, 4 blockIdx.x + w), lane = voxel (split^3 <= 64).
 // otherwise:      grid (nb * passes, nb, nb), the workgroup owns voxels [1024 pass, 1024 (pass + 1)) of block (blockIdx.z, blockIdx.y, blockIdx.x / passes).
@@ -249,13 +151,7 @@ extern "C" int dgs_gaussian_field(const DgsFieldArgs* a, dgs_stream_t stream) {
     const dgs::FieldWs ws(a->workspace, a->N, a->nb);
     if (a->workspace_bytes < ws.bytes) return DGS_ERR_INVALID_ARGUMENT;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t cells = (int64_t)a->nb * a->nb * a->nb;
-    const dim3 per_gaussian((a->N + dgs::FIELD_WG - 1) / dgs::FIELD_WG);
-    if (hipMemsetAsync(ws.count, 0, 4 * cells, st) != hipSuccess) return DGS_ERR_DEVICE;
-    hipLaunchKernelGGL(dgs::field_key_kernel, per_gaussian, dim3(dgs::FIELD_WG), 0, st, *a, ws);
-    hipLaunchKernelGGL(dgs::field_scan_kernel, dim3(1), dim3(1024), 0, st, ws, cells);
-    hipLaunchKernelGGL(dgs::field_scatter_kernel, per_gaussian, dim3(dgs::FIELD_WG), 0, st, *a, ws);
-    hipLaunchKernelGGL(dgs::field_prepare_kernel, per_gaussian, dim3(dgs::FIELD_WG), 0, st, *a, ws);
+    if (!dgs::field_bin_gaussians(*a, ws, st)) return DGS_ERR_DEVICE;
     const int s3 = a->split * a->split * a->split;
     if (a->split <= 4) {
         const dim3 grid((a->nb + dgs::FIELD_ZB - 1) / dgs::FIELD_ZB, a->nb, a->nb);

@@ -564,8 +564,30 @@ def _declare_mesh_decimate(L):
     return L
 
 
+class DgsMeshAttrArgs(ctypes.Structure):
+    _fields_ = [("V", ctypes.c_int64), ("N", ctypes.c_int32), ("nb", ctypes.c_int32), ("reach", ctypes.c_int32),
+                ("mesh_scale", ctypes.c_float), ("scaling_modifier", ctypes.c_float), ("xyz", ctypes.c_void_p), ("scaling", ctypes.c_void_p),
+                ("rotation", ctypes.c_void_p), ("opacity", ctypes.c_void_p), ("attr", ctypes.c_void_p), ("points", ctypes.c_void_p),
+                ("density", ctypes.c_void_p), ("attr_out", ctypes.c_void_p), ("gradient", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_int64)]
+
+
+# every symbol include/dgs_mesh_attr.h declares (checked by tests/test_mesh_attr.py)
+MESH_ATTR_SYMBOLS = ["dgs_mesh_attributes", "dgs_mesh_attributes_workspace_bytes"]
+
+
+def _declare_mesh_attr(L):
+    if not all(hasattr(L, name) for name in MESH_ATTR_SYMBOLS):          # a build that predates the attributes (an A/B side): consumers.py refuses it there
+        return L
+    L.dgs_mesh_attributes.restype = ctypes.c_int
+    L.dgs_mesh_attributes.argtypes = [ctypes.POINTER(DgsMeshAttrArgs), ctypes.c_void_p]
+    L.dgs_mesh_attributes_workspace_bytes.restype = ctypes.c_int64
+    L.dgs_mesh_attributes_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
+    return L
+
+
 _declare_raster = _declare
 
 
-def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up + decimation prototypes on one library)
-    return _declare_mesh_decimate(_declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L))))))))))
+def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up + decimation + attributes prototypes on one library)
+    return _declare_mesh_attr(_declare_mesh_decimate(_declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L)))))))))))

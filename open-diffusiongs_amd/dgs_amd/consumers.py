@@ -239,8 +239,9 @@ class Mesh:
     """What GaussianModel.extract_mesh returns: vertices float32 [V, 3] in the reference's normalised cube [-1, 1]^3 and faces int32
     [F, 3], both on the model's device (the reference wraps the same two arrays in a trimesh.Trimesh)."""
 
-    def __init__(self, vertices, faces):
+    def __init__(self, vertices, faces, colors=None, normals=None, density=None):
         self.vertices, self.faces = vertices, faces
+        self.colors, self.normals, self.density = colors, normals, density      # per vertex, of extract_mesh(attributes=True); else None
 
     def __repr__(self):
         return f"Mesh(vertices={tuple(self.vertices.shape)}, faces={tuple(self.faces.shape)}, device={self.vertices.device})"
@@ -447,7 +448,79 @@ def decimate_mesh(vertices, faces, target, n_max=1024, return_n=False, lib=None)
     return (out_v, out_f, lo) if return_n else (out_v, out_f)
 
 
-def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0, decimate_target=0):
+def mesh_attributes(pc, points, num_blocks=64, reach=2, attr=None, want=("colors", "normals", "density"), lib=None):
+    """What the Gaussians of `pc` say at `points` float32 [V, 3] of the normalised cube [-1, 1]^3 (the vertices of extract_mesh): a dict
+    with the entries of `want`, on pc's device --
+        "density"  [V]     sum of sigmoid(opacity) * exp(power) over the Gaussians in the window of `reach` cells (pitch 2 / num_blocks)
+                           around the point's cell,
+        "colors"   [V, 3]  the mean of `attr` [N, 3] under those weights, 0 where the density is 0; attr defaults to the
+                           view-independent colour clamp(0.5 + C0 * f_dc, 0, 1), the reference's SH2RGB at degree 0,
+        "normals"  [V, 3]  -gradient / |gradient| of the density, 0 where the gradient is 0: it points out of the object, to the side
+                           the faces of marching_cubes turn to.
+    The definition and the summation order are in include/dgs_mesh_attr.h (csrc/mesh_attr.hip): the same inputs give the same bytes,
+    and a point's values do not depend on the other points of the call.  The centres are normalised with the expressions of
+    extract_fields, and pc.mesh_center / pc.mesh_scale are set the same way, so the call stands on its own.  One C call on the current
+    stream, no host synchronisation."""
+    from . import _native
+    want = tuple(want)
+    if not want or any(w not in ("colors", "normals", "density") for w in want):
+        raise ValueError(f"mesh_attributes: want must name some of 'colors', 'normals', 'density', got {want}")
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError(f"mesh_attributes: points must be float32 [V, 3], got {points.dtype} {tuple(points.shape)}")
+    with torch.no_grad():
+        xyz = pc.get_xyz.float()
+        if xyz.shape[0] == 0:
+            raise ValueError("mesh_attributes: no Gaussians (all filtered away?)")
+        if points.device != xyz.device:
+            raise ValueError(f"mesh_attributes: the model on {xyz.device}, points on {points.device}")
+        L = lib or _native.lib()
+        if not all(hasattr(L, name) for name in _native.MESH_ATTR_SYMBOLS):
+            raise RuntimeError("mesh_attributes: this build of the library predates the mesh attributes -- rebuild it (`python -m dgs_amd.build`)")
+        mn, mx = xyz.amin(0), xyz.amax(0)
+        pc.mesh_center = (mn + mx) / 2
+        pc.mesh_scale = 1.8 / (mx - mn).amax().item()
+        dev = xyz.device
+        xyzs = ((xyz - pc.mesh_center) * pc.mesh_scale).contiguous()
+        scaling, rotation, opacity = (t.detach().float().contiguous() for t in (pc._scaling, pc._rotation, pc._opacity))
+        if attr is None:
+            attr = (0.5 + C0 * pc._features_dc.detach().float().reshape(-1, 3)).clamp(0, 1)
+        attr = attr.detach().float().contiguous()
+        if attr.shape != (xyz.shape[0], 3) or attr.device != dev:
+            raise ValueError(f"mesh_attributes: attr must be [N, 3] = [{xyz.shape[0]}, 3] on {dev}, got {tuple(attr.shape)} on {attr.device}")
+        points = points.detach().contiguous()
+        a = _native.DgsMeshAttrArgs()
+        a.V, a.N, a.nb, a.reach = points.shape[0], xyz.shape[0], int(num_blocks), int(reach)
+        a.mesh_scale = pc.mesh_scale
+        a.scaling_modifier = 1.0 if pc.scaling_modifier is None else float(pc.scaling_modifier)
+        a.workspace_bytes = L.dgs_mesh_attributes_workspace_bytes(a.N, a.nb, a.V)
+        if a.workspace_bytes <= 0:
+            raise ValueError(f"mesh_attributes: unsupported size (num_blocks {num_blocks} in [1, 256], V = {a.V} at most 2^30)")
+        ws = torch.empty(a.workspace_bytes if a.V else 0, dtype=torch.uint8, device=dev)
+        density = torch.empty(a.V, dtype=torch.float32, device=dev) if "density" in want else None
+        colors = torch.empty((a.V, 3), dtype=torch.float32, device=dev) if "colors" in want else None
+        gradient = torch.empty((a.V, 3), dtype=torch.float32, device=dev) if "normals" in want else None
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        a.xyz, a.scaling, a.rotation, a.opacity, a.attr, a.points, a.workspace = (ptr(t) for t in (xyzs, scaling, rotation, opacity, attr, points, ws))
+        a.density, a.attr_out, a.gradient = ptr(density), ptr(colors), ptr(gradient)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if xyz.is_cuda else None
+        rc = L.dgs_mesh_attributes(ctypes.byref(a), stream)
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"dgs_mesh_attributes failed: {rc} ({_native.status_string(L, rc)})")
+        if xyz.is_cuda:
+            for t in (xyzs, scaling, rotation, opacity, attr, points, ws):
+                t.record_stream(torch.cuda.current_stream(dev))
+        out = {}
+        if colors is not None:
+            out["colors"] = colors
+        if gradient is not None:
+            norm = torch.sqrt((gradient * gradient).sum(dim=1, keepdim=True))
+            out["normals"] = torch.where(norm > 0, -gradient / norm, torch.zeros_like(gradient))
+        if density is not None:
+            out["density"] = density
+    return out
+
+
+def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0, decimate_target=0, attributes=False):
     """gs_core.py:855-869: extract_fields (sets pc.mesh_center / pc.mesh_scale), marching cubes at density_thresh,
     vertices / (resolution - 1) * 2 - 1 -> Mesh on pc's device.  min_f / min_d > 0 then drop the floaters as the first two
     filters of the reference's clean_mesh do (remove_small_components on the mesh in [-1, 1]^3, which is what clean_mesh sees; the
@@ -455,7 +528,9 @@ def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=No
     a mesh of more faces down to at most that many by vertex clustering on the device (decimate_mesh; the reference's value is 1e5,
     by pymeshlab's quadric edge collapse); 0, the default, does not enter that path, and with all three 0 the raw level set is
     returned.  The rest of clean_mesh (merging close vertices, non-manifold repair, remeshing: pymeshlab) is not part of this: hand it
-    mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy() (INTEGRATION.md)."""
+    mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy().  attributes=True then evaluates mesh_attributes at the
+    final vertices (same num_blocks, reach 2) and returns them as mesh.colors / mesh.normals / mesh.density; False, the default,
+    launches nothing for them and leaves the three None."""
     occ = extract_fields(pc, resolution, num_blocks, lib=lib)
     vertices, triangles = marching_cubes(occ, density_thresh, lib=lib)
     vertices = vertices / (resolution - 1.0) * 2 - 1
@@ -463,11 +538,24 @@ def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=No
         vertices, triangles = remove_small_components(vertices, triangles, min_f=min_f, min_d=min_d, lib=lib)
     if decimate_target:
         vertices, triangles = decimate_mesh(vertices, triangles, decimate_target, lib=lib)
+    if attributes:
+        at = mesh_attributes(pc, vertices, num_blocks=num_blocks, lib=lib)
+        return Mesh(vertices, triangles, at["colors"], at["normals"], at["density"])
     return Mesh(vertices, triangles)
 
 
-def save_mesh_ply(path, vertices, faces):
-    """Binary little-endian PLY: element vertex (x y z float), element face (list uchar int vertex_indices), triangles only."""
+def mesh_color_bytes(colors):
+    """float colours -> uint8 as the PLY stores them: floor(clamp(c, 0, 1) * 255 + 0.5), evaluated in fp64; a NaN (the colour of a
+    vertex at a NaN point) becomes 0."""
+    c = np.asarray(colors, dtype=np.float64)
+    c = np.clip(np.where(np.isnan(c), 0.0, c), 0.0, 1.0)
+    return np.floor(c * 255.0 + 0.5).astype(np.uint8)
+
+
+def save_mesh_ply(path, vertices, faces, colors=None, normals=None):
+    """Binary little-endian PLY: element vertex (x y z float; with `normals` [V, 3] also nx ny nz float; with `colors` [V, 3] also
+    red green blue uchar -- float colours go through mesh_color_bytes, uint8 ones are written as they are), element face (list uchar
+    int vertex_indices), triangles only.  Without colours and normals the bytes are what this function has always written."""
     n = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
     v, f = n(vertices).astype("<f4", copy=False).reshape(-1, 3), n(faces).astype("<i4", copy=False).reshape(-1, 3)
     d = os.path.dirname(path)
@@ -475,17 +563,32 @@ def save_mesh_ply(path, vertices, faces):
         os.makedirs(d, exist_ok=True)
     el = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
     el["n"], el["i"] = 3, f
-    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y",
-              "property float z", f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    fields, props = [("p", "<f4", (3,))], ["property float x", "property float y", "property float z"]
+    if normals is not None:
+        fields.append(("nrm", "<f4", (3,)))
+        props += ["property float nx", "property float ny", "property float nz"]
+    if colors is not None:
+        fields.append(("rgb", "u1", (3,)))
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    vert = np.empty(v.shape[0], dtype=fields)
+    vert["p"] = v
+    if normals is not None:
+        vert["nrm"] = n(normals).astype("<f4", copy=False).reshape(v.shape[0], 3)
+    if colors is not None:
+        c = n(colors).reshape(v.shape[0], 3)
+        vert["rgb"] = c if c.dtype == np.uint8 else mesh_color_bytes(c)
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"] + props + [
+        f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     with open(path, "wb") as out:
         out.write(("\n".join(header) + "\n").encode("ascii"))
-        out.write(np.ascontiguousarray(v).tobytes())
+        out.write(vert.tobytes())
         out.write(el.tobytes())
 
 
-def load_mesh_ply(path):
-    """-> (vertices float32 [V, 3], faces int32 [F, 3]) numpy arrays of a file written by save_mesh_ply (float x y z vertices, triangle
-    faces as `list uchar int`)."""
+def load_mesh_ply(path, return_attributes=False):
+    """-> (vertices float32 [V, 3], faces int32 [F, 3]) numpy arrays of a file written by save_mesh_ply (float x y z vertices, optionally
+    float nx ny nz and uchar red green blue after them, triangle faces as `list uchar int`).  With return_attributes a third item: a
+    dict with "normals" float32 [V, 3] and "colors" uint8 [V, 3] where the file has them."""
     with open(path, "rb") as f:
         assert f.readline().strip() == b"ply"
         assert f.readline().split()[:2] == [b"format", b"binary_little_endian"], "only binary little-endian files (what save_mesh_ply writes)"
@@ -499,9 +602,22 @@ def load_mesh_ply(path):
                 counts[cur], props[cur] = int(tok[2]), []
             elif tok[0] == "property":
                 props[cur].append(tok[1:])
-        assert list(counts) == ["vertex", "face"] and props["vertex"] == [["float", "x"], ["float", "y"], ["float", "z"]], props
+        xyz, nrm, rgb = [["float", k] for k in "xyz"], [["float", k] for k in ("nx", "ny", "nz")], [["uchar", k] for k in ("red", "green", "blue")]
+        pv = props["vertex"]
+        has_n = pv[3:6] == nrm
+        has_c = pv[3 + 3 * has_n:] == rgb
+        assert list(counts) == ["vertex", "face"] and pv == xyz + nrm * has_n + rgb * has_c, props
         assert props["face"] == [["list", "uchar", "int", "vertex_indices"]], props
-        v = np.frombuffer(f.read(12 * counts["vertex"]), dtype="<f4").reshape(-1, 3)
+        fields = [("p", "<f4", (3,))] + [("nrm", "<f4", (3,))] * has_n + [("rgb", "u1", (3,))] * has_c
+        vert = np.frombuffer(f.read(np.dtype(fields).itemsize * counts["vertex"]), dtype=fields)
         el = np.frombuffer(f.read(13 * counts["face"]), dtype=[("n", "u1"), ("i", "<i4", (3,))])
-        assert v.shape[0] == counts["vertex"] and el.shape[0] == counts["face"] and bool((el["n"] == 3).all())
-        return v.astype(np.float32), np.ascontiguousarray(el["i"]).astype(np.int32)
+        assert vert.shape[0] == counts["vertex"] and el.shape[0] == counts["face"] and bool((el["n"] == 3).all())
+        v, faces = np.ascontiguousarray(vert["p"]).astype(np.float32).reshape(-1, 3), np.ascontiguousarray(el["i"]).astype(np.int32)
+        if not return_attributes:
+            return v, faces
+        attrs = {}
+        if has_n:
+            attrs["normals"] = np.ascontiguousarray(vert["nrm"]).astype(np.float32)
+        if has_c:
+            attrs["colors"] = np.ascontiguousarray(vert["rgb"]).astype(np.uint8)
+        return v, faces, attrs
