@@ -586,8 +586,29 @@ def _declare_mesh_attr(L):
     return L
 
 
+class DgsMeshSmoothArgs(ctypes.Structure):
+    _fields_ = [("V", ctypes.c_int64), ("F", ctypes.c_int64), ("vertices", ctypes.c_void_p), ("faces", ctypes.c_void_p),
+                ("fixed", ctypes.c_void_p), ("lam", ctypes.c_double), ("mu", ctypes.c_double), ("iterations", ctypes.c_int32),
+                ("counts", ctypes.c_void_p), ("out_vertices", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_int64)]
+
+
+# every symbol include/dgs_mesh_smooth.h declares (checked by tests/test_mesh_smooth.py)
+MESH_SMOOTH_SYMBOLS = ["dgs_mesh_smooth", "dgs_mesh_smooth_workspace_bytes"]
+
+
+def _declare_mesh_smooth(L):
+    if not all(hasattr(L, name) for name in MESH_SMOOTH_SYMBOLS):        # a build that predates the smoothing (an A/B side): consumers.py refuses it there
+        return L
+    L.dgs_mesh_smooth.restype = ctypes.c_int
+    L.dgs_mesh_smooth.argtypes = [ctypes.POINTER(DgsMeshSmoothArgs), ctypes.c_void_p]
+    L.dgs_mesh_smooth_workspace_bytes.restype = ctypes.c_int64
+    L.dgs_mesh_smooth_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    return L
+
+
 _declare_raster = _declare
 
 
-def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up + decimation + attributes prototypes on one library)
-    return _declare_mesh_attr(_declare_mesh_decimate(_declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L)))))))))))
+def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up + decimation + attributes + smoothing prototypes on one library)
+    return _declare_mesh_smooth(_declare_mesh_attr(_declare_mesh_decimate(_declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L))))))))))))

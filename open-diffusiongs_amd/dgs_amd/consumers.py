@@ -16,10 +16,13 @@ and of diffusionGS/utils/mesh_utils.py clean_mesh :119-125  (the two pymeshlab f
                                    decimate_mesh :44-85     (pymeshlab's quadric edge collapse, order-dependent; here its commented
                                                              alternative, vertex clustering, with an order-free definition:
                                                              cluster_vertices / decimate_mesh, csrc/mesh_decimate.hip)
+                                   clean_mesh :133, decimate_mesh :71  (ms.apply_coord_taubin_smoothing(), the commented alternative
+                                                             of their remeshing; here smooth_mesh, csrc/mesh_smooth.hip)
 The reference writes / reads the file through the `plyfile` package (binary_little_endian 1.0, one "vertex" element, scalar
 properties in dtype order); that byte layout is restated here with numpy structured arrays -- no extra dependency.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -448,6 +451,66 @@ def decimate_mesh(vertices, faces, target, n_max=1024, return_n=False, lib=None)
     return (out_v, out_f, lo) if return_n else (out_v, out_f)
 
 
+def smooth_mesh(vertices, faces, iterations=10, lam=0.5, mu=-0.53, fixed=None, return_counts=False, lib=None):
+    """Taubin smoothing of the vertices on the mesh's device (include/dgs_mesh_smooth.h, csrc/mesh_smooth.hip; MeshLab's
+    apply_coord_taubin_smoothing with the cotangent weights off, the commented alternative of the remeshing in the reference's
+    clean_mesh / decimate_mesh, at MeshLab's defaults): `iterations` times a pass with weight lam, then one with weight mu, each moving
+    every vertex towards (lam > 0) or away from (mu < 0) the mean of the other corners of its faces, all reads from the pass's input.
+    mu = 0 is plain Laplacian smoothing, which shrinks the object.  vertices float32 [V, 3], faces int32 [F, 3], fixed None or a
+    bool / uint8 [V] of vertices that stay -> vertices float32 [V, 3] on the same device; the faces are untouched.  Invalid faces (an
+    index outside [0, V)) and null faces (two equal indices) are ignored; a vertex no such face names, or one that more than 16,384
+    name, keeps its bytes.  With return_counts also [invalid faces, null faces, vertices over that cap, unreferenced vertices], the
+    call's only host synchronisation.  The same input gives the same bytes.  Not part of this: border handling (an open mesh shrinks
+    at its border), cotangent weights, remeshing, non-manifold repair.  One C call on the current stream."""
+    from . import _native
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise ValueError(f"smooth_mesh: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"smooth_mesh: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+    if faces.device != vertices.device:
+        raise ValueError(f"smooth_mesh: vertices on {vertices.device}, faces on {faces.device}")
+    if int(iterations) != iterations or not 0 <= iterations <= 1 << 20:
+        raise ValueError(f"smooth_mesh: iterations must be an integer in [0, 2^20], got {iterations}")
+    if not (math.isfinite(lam) and math.isfinite(mu)):
+        raise ValueError(f"smooth_mesh: lam and mu must be finite, got {lam}, {mu}")
+    if fixed is not None:
+        if fixed.dim() != 1 or fixed.shape[0] != vertices.shape[0] or fixed.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"smooth_mesh: fixed must be bool or uint8 [V] = [{vertices.shape[0]}], got {fixed.dtype} {tuple(fixed.shape)}")
+        if fixed.device != vertices.device:
+            raise ValueError(f"smooth_mesh: vertices on {vertices.device}, fixed on {fixed.device}")
+    with torch.no_grad():
+        L = lib or _native.lib()
+        if not all(hasattr(L, name) for name in _native.MESH_SMOOTH_SYMBOLS):
+            raise RuntimeError("smooth_mesh: this build of the library predates the mesh smoothing -- rebuild it (`python -m dgs_amd.build`)")
+        dev = vertices.device
+        vertices, faces = vertices.detach().contiguous(), faces.detach().contiguous()
+        if fixed is not None:
+            fixed = fixed.detach().contiguous().view(torch.uint8)           # a bool is one byte, 0 or 1
+        a = _native.DgsMeshSmoothArgs()
+        a.V, a.F = vertices.shape[0], faces.shape[0]
+        a.lam, a.mu, a.iterations = float(lam), float(mu), int(iterations)
+        a.workspace_bytes = L.dgs_mesh_smooth_workspace_bytes(a.V, a.F)
+        if a.workspace_bytes <= 0:
+            raise ValueError(f"smooth_mesh: unsupported size V = {a.V}, F = {a.F} (at most 2^30 and 2^29)")
+        ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty((a.V, 3), dtype=torch.float32, device=dev)
+        counts = torch.empty(4, dtype=torch.int32, device=dev) if return_counts else None   # the call writes uint32 [4]
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        a.vertices, a.faces, a.fixed, a.out_vertices, a.counts = ptr(vertices), ptr(faces), ptr(fixed), ptr(out), ptr(counts)
+        a.workspace = ctypes.c_void_p(ws.data_ptr())
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if vertices.is_cuda else None
+        rc = L.dgs_mesh_smooth(ctypes.byref(a), stream)
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"dgs_mesh_smooth failed: {rc} ({_native.status_string(L, rc)})")
+        if vertices.is_cuda:
+            for t in (vertices, faces, fixed, ws):
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream(dev))
+        if return_counts:
+            return out, [c & 0xFFFFFFFF for c in counts.tolist()]           # the one host synchronisation
+    return out
+
+
 def mesh_attributes(pc, points, num_blocks=64, reach=2, attr=None, want=("colors", "normals", "density"), lib=None):
     """What the Gaussians of `pc` say at `points` float32 [V, 3] of the normalised cube [-1, 1]^3 (the vertices of extract_mesh): a dict
     with the entries of `want`, on pc's device --
@@ -520,7 +583,8 @@ def mesh_attributes(pc, points, num_blocks=64, reach=2, attr=None, want=("colors
     return out
 
 
-def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0, decimate_target=0, attributes=False):
+def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0, decimate_target=0, attributes=False,
+                 smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53):
     """gs_core.py:855-869: extract_fields (sets pc.mesh_center / pc.mesh_scale), marching cubes at density_thresh,
     vertices / (resolution - 1) * 2 - 1 -> Mesh on pc's device.  min_f / min_d > 0 then drop the floaters as the first two
     filters of the reference's clean_mesh do (remove_small_components on the mesh in [-1, 1]^3, which is what clean_mesh sees; the
@@ -528,7 +592,9 @@ def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=No
     a mesh of more faces down to at most that many by vertex clustering on the device (decimate_mesh; the reference's value is 1e5,
     by pymeshlab's quadric edge collapse); 0, the default, does not enter that path, and with all three 0 the raw level set is
     returned.  The rest of clean_mesh (merging close vertices, non-manifold repair, remeshing: pymeshlab) is not part of this: hand it
-    mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy().  attributes=True then evaluates mesh_attributes at the
+    mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy().  smooth_iterations > 0 then smooths the vertices of that
+    mesh with that many Taubin iterations of weights smooth_lambda, smooth_mu (smooth_mesh: the commented alternative of the reference's
+    remeshing; the faces stay); 0, the default, does not enter that path.  attributes=True then evaluates mesh_attributes at the
     final vertices (same num_blocks, reach 2) and returns them as mesh.colors / mesh.normals / mesh.density; False, the default,
     launches nothing for them and leaves the three None."""
     occ = extract_fields(pc, resolution, num_blocks, lib=lib)
@@ -538,6 +604,8 @@ def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=No
         vertices, triangles = remove_small_components(vertices, triangles, min_f=min_f, min_d=min_d, lib=lib)
     if decimate_target:
         vertices, triangles = decimate_mesh(vertices, triangles, decimate_target, lib=lib)
+    if smooth_iterations:
+        vertices = smooth_mesh(vertices, triangles, smooth_iterations, smooth_lambda, smooth_mu, lib=lib)
     if attributes:
         at = mesh_attributes(pc, vertices, num_blocks=num_blocks, lib=lib)
         return Mesh(vertices, triangles, at["colors"], at["normals"], at["density"])

@@ -149,17 +149,19 @@ class GaussianModel:
         from . import consumers
         return consumers.extract_fields(self, resolution, num_blocks, relax_ratio, lib)
 
-    def extract_mesh(self, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0, decimate_target=0, attributes=False):
+    def extract_mesh(self, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0, decimate_target=0, attributes=False,
+                     smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53):
         """gs_core.py:855-869 -> consumers.Mesh(vertices [V, 3] in [-1, 1]^3, faces [F, 3]) on the model's device: extract_fields,
         then marching cubes on the device (csrc/mesh.hip); sets self.mesh_center / self.mesh_scale as extract_fields does.
         min_f / min_d > 0 drop the small components on the device as well (csrc/mesh_clean.hip; the reference's clean_mesh uses
         min_f=64, min_d=20).  decimate_target > 0 then reduces a mesh of more faces to at most that many by vertex clustering on the
         device (consumers.decimate_mesh, csrc/mesh_decimate.hip; the reference's value is 1e5, by quadric edge collapse).  The
-        default 0, 0, 0 returns the raw level set.  attributes=True also fills the mesh's colors / normals / density at the final
-        vertices (mesh_attributes)."""
+        default 0, 0, 0 returns the raw level set.  smooth_iterations > 0 then smooths the vertices with that many Taubin iterations
+        of weights smooth_lambda, smooth_mu (consumers.smooth_mesh, csrc/mesh_smooth.hip); 0, the default, does not enter that path.
+        attributes=True also fills the mesh's colors / normals / density at the final vertices (mesh_attributes)."""
         from . import consumers
         return consumers.extract_mesh(self, density_thresh, resolution, num_blocks, lib, min_f=min_f, min_d=min_d, decimate_target=decimate_target,
-                                      attributes=attributes)
+                                      attributes=attributes, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
 
     def mesh_attributes(self, points, num_blocks=64, reach=2, attr=None, want=("colors", "normals", "density"), lib=None):
         """Colour, outward normal and density of the Gaussians at `points` [V, 3] of the normalised cube (the vertices of extract_mesh)
