@@ -59,7 +59,9 @@ int dgs_resize_bilinear_backward(const DgsResizeArgs* args, dgs_stream_t stream)
  * is the only active term of the first training steps of configs/diffusionGS_rel.yaml), forward values and the gradient with
  * respect to `aligned` in two passes over the tensors, every sum reduced in a fixed order:
  *   points-distribution loss, per sample b:
- *       dist = |aligned - ray_o|_2 per pixel; per (b, view): mean and UNBIASED std of dist over the view's pixels (detached);
+ *       dist = |aligned - ray_o|_2 per pixel; per (b, view): mean and UNBIASED std of dist over the view's pixels (detached; summed
+ *       on dist minus the view's first distance, so that nearly constant distances -- those first steps -- do not cancel in fp32; a
+ *       view of one pixel has std 0);
  *       target = (dist - mean) / (std + 1e-8) * 0.5 + |ray_o|_2;   pointsdist[b] = mean over (v, h, w) of (dist - target)^2
  *   xyz loss, one scalar for the batch (optional: gt and masks given):
  *       xyz = sum((aligned * m - gt * m)^2) / sum(m),  m = masks [B, V, 1, H, W] broadcast over the three coordinates

@@ -97,14 +97,23 @@ __global__ __launch_bounds__(256) void resize_bilinear_backward_kernel(DgsResize
 // ------------------------------------------------------------------------------------------------------------------
 // Points-distribution + xyz loss (dgs_loss.h DgsPointsLossArgs).  A (sample, view) plane of H W pixels is cut into
 // DGS_LOSS_CHUNKS chunks; a workgroup reduces one chunk; chunk sums are added in index order by the finishing kernels.
-// workspace layout (floats): stat [B V][CH][4] (sum dist, sum dist^2, masked squared error, mask sum) | moments [B V][2] (mean,
+// workspace layout (floats): stat [B V][CH][4] (sum s, sum s^2, masked squared error, mask sum) | moments [B V][2] (mean of s,
 // 1 / (std + 1e-8)) | xyz totals [2] | pd [B V][CH] (sum (dist - target)^2)
+// s = dist - d0, d0 = the distance at the plane's pixel 0 (plane_dist0: every kernel recomputes it from the same two points, the same
+// bits).  Early in training the distances of a plane are nearly constant (the points-distribution term is the only active one then,
+// dgs_loss.h), and fp32 sums of dist and dist^2 cancel in sum d^2 - n mean^2: at std / mean = 2e-4 the loss was off by 10 %.  The shifted
+// values are of the size of the spread itself, their subtraction from d0 is exact or nearly so, and dist - mean = s - mean(s).
 // ------------------------------------------------------------------------------------------------------------------
 struct PointsWs {
     float *stat, *moments, *xyz_tot, *pd;
     __host__ __device__ PointsWs(float* w, int BV) : stat(w), moments(w + (size_t)BV * DGS_LOSS_CHUNKS * 4), xyz_tot(moments + (size_t)BV * 2),
                                                      pd(xyz_tot + 2) {}
 };
+
+__device__ __forceinline__ float plane_dist0(const float* p, const float* o, long long HW) {
+    const float dx = p[0] - o[0], dy = p[HW] - o[HW], dz = p[2 * HW] - o[2 * HW];
+    return sqrtf(dx * dx + dy * dy + dz * dz);
+}
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
     red[threadIdx.x] = v;
@@ -125,10 +134,11 @@ __global__ __launch_bounds__(256) void points_stats_kernel(DgsPointsLossArgs a) 
     const long long lo = (long long)chunk * per, hi = lo + per < HW ? lo + per : HW;
     const float* p = a.aligned + (size_t)bv * 3 * HW;
     const float* o = a.ray_o + (size_t)bv * 3 * HW;
+    const float d0 = plane_dist0(p, o, HW);
     float s1 = 0.f, s2 = 0.f, se = 0.f, sm = 0.f;
     for (long long i = lo + threadIdx.x; i < hi; i += 256) {
         const float dx = p[i] - o[i], dy = p[HW + i] - o[HW + i], dz = p[2 * HW + i] - o[2 * HW + i];
-        const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+        const float d = sqrtf(dx * dx + dy * dy + dz * dz) - d0;
         s1 += d; s2 += d * d;
         if (a.gt) {
             const float m = a.masks[(size_t)bv * HW + i];
@@ -145,7 +155,7 @@ __global__ __launch_bounds__(256) void points_stats_kernel(DgsPointsLossArgs a) 
     }
 }
 
-// one thread per (sample, view): mean / unbiased std of dist; thread 0 also totals the xyz sums over the batch
+// one thread per (sample, view): mean of dist - d0 and the unbiased std of dist; thread 0 also totals the xyz sums over the batch
 __global__ void points_moments_kernel(DgsPointsLossArgs a) {
     const int bv = blockIdx.x * blockDim.x + threadIdx.x, BV = a.B * a.V;
     PointsWs w(a.workspace, BV);
@@ -174,6 +184,7 @@ __global__ __launch_bounds__(256) void points_loss_kernel(DgsPointsLossArgs a) {
     const float mean = w.moments[2 * bv], istd = w.moments[2 * bv + 1];
     const float* p = a.aligned + (size_t)bv * 3 * HW;
     const float* o = a.ray_o + (size_t)bv * 3 * HW;
+    const float d0 = plane_dist0(p, o, HW);
     float* g = a.grad ? a.grad + (size_t)bv * 3 * HW : nullptr;
     const float wpd = (a.w_pointsdist ? a.w_pointsdist[b] : 0.f) * 2.0f / (float)((long long)a.V * HW);
     const float wx = a.gt ? a.w_xyz * 2.0f / w.xyz_tot[1] : 0.f;
@@ -182,7 +193,7 @@ __global__ __launch_bounds__(256) void points_loss_kernel(DgsPointsLossArgs a) {
         const float ox = o[i], oy = o[HW + i], oz = o[2 * HW + i];
         const float dx = p[i] - ox, dy = p[HW + i] - oy, dz = p[2 * HW + i] - oz;
         const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float target = (d - mean) * istd * 0.5f + sqrtf(ox * ox + oy * oy + oz * oz);
+        const float target = ((d - d0) - mean) * istd * 0.5f + sqrtf(ox * ox + oy * oy + oz * oz);
         const float e = d - target;
         acc += e * e;
         if (g) {
