@@ -7,7 +7,8 @@
  *     compute_psnr: clamp both to [0, 1] first                                                               :399-402
  * and the autograd backward of the lambda_mse term (d/d rendering = 2 (rendering - target) * grad_scale / n).
  * and the SSIM term (`SsimLoss`, :216-234; evaluated over all b * v views on every step, :317-321): DgsSsimArgs below.
- * LPIPS (a VGG network that needs weights) is out of scope; its input path is DgsResizeArgs.  One pass over the images, per-sample
+ * LPIPS (a VGG network that needs weights) is out of scope; its input path is DgsResizeArgs, and the trainer has a slot for a
+ * network supplied by the user (DataParallelTrainer.configure_objective(perceptual=...)).  One pass over the images, per-sample
  * sums reduced in a fixed order (deterministic), no host synchronisation.  Device pointers; returns DGS_OK or a negative DgsStatus.
  */
 #ifndef DGS_LOSS_H
@@ -65,7 +66,9 @@ int dgs_resize_bilinear_backward(const DgsResizeArgs* args, dgs_stream_t stream)
  *       target = (dist - mean) / (std + 1e-8) * 0.5 + |ray_o|_2;   pointsdist[b] = mean over (v, h, w) of (dist - target)^2
  *   xyz loss, one scalar for the batch (optional: gt and masks given):
  *       xyz = sum((aligned * m - gt * m)^2) / sum(m),  m = masks [B, V, 1, H, W] broadcast over the three coordinates
- *   grad = w_pointsdist[b] * d pointsdist[b] / d aligned + w_xyz * d xyz / d aligned      (optional)                            */
+ *   grad = w_pointsdist[b] * d pointsdist[b] / d aligned + w_xyz * d xyz / d aligned      (optional)
+ * Called by the trainer's objective (dgs_amd.train.DataParallelTrainer.train_step through losses.points_losses /
+ * points_losses_part), whose gradient reaches dgs_dit_backward as d / d img_aligned_xyz.                                         */
 typedef struct DgsPointsLossArgs {
     int32_t B, V, H, W;
     const float* aligned;      /* f32 [B, V, 3, H, W]                                                       */
@@ -78,6 +81,11 @@ typedef struct DgsPointsLossArgs {
     float w_xyz;               /* upstream gradient of xyz                                                  */
     float* grad;               /* optional out f32 [B, V, 3, H, W]                                          */
     float* workspace;          /* f32 [dgs_points_loss_workspace_floats(B, V)]                               */
+    /* appended (a zero-initialised tail is the call as it was): what a trainer needs to evaluate a batch in micro-batches without
+       reading a device value back to the host */
+    const float* xyz_denominator; /* optional device f32 [1]: stands in for sum(m) in xyz and its gradient (the mask sum of the WHOLE
+                                     batch when this call sees a part of it: the parts' xyz then add up to the batch's)  */
+    const float* w_xyz_dev;    /* optional device f32 [1]: multiplies w_xyz (an upstream gradient that lives on the device) */
 } DgsPointsLossArgs;
 
 int64_t dgs_points_loss_workspace_floats(int32_t B, int32_t V);

@@ -170,6 +170,7 @@ __global__ void points_moments_kernel(DgsPointsLossArgs a) {
     if (bv == 0 && a.gt) {
         double se = 0.0, sm = 0.0;
         for (int i = 0; i < BV * DGS_LOSS_CHUNKS; ++i) { se += w.stat[(size_t)i * 4 + 2]; sm += w.stat[(size_t)i * 4 + 3]; }
+        if (a.xyz_denominator) sm = (double)a.xyz_denominator[0];         // the caller's sum(m): a micro-batch of a larger batch
         w.xyz_tot[0] = (float)se; w.xyz_tot[1] = (float)sm;
         a.xyz[0] = (float)(se / sm);
     }
@@ -187,7 +188,8 @@ __global__ __launch_bounds__(256) void points_loss_kernel(DgsPointsLossArgs a) {
     const float d0 = plane_dist0(p, o, HW);
     float* g = a.grad ? a.grad + (size_t)bv * 3 * HW : nullptr;
     const float wpd = (a.w_pointsdist ? a.w_pointsdist[b] : 0.f) * 2.0f / (float)((long long)a.V * HW);
-    const float wx = a.gt ? a.w_xyz * 2.0f / w.xyz_tot[1] : 0.f;
+    const float up = a.w_xyz_dev ? a.w_xyz * a.w_xyz_dev[0] : a.w_xyz;
+    const float wx = a.gt ? up * 2.0f / w.xyz_tot[1] : 0.f;
     float acc = 0.f;
     for (long long i = lo + threadIdx.x; i < hi; i += 256) {
         const float ox = o[i], oy = o[HW + i], oz = o[2 * HW + i];

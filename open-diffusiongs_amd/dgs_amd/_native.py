@@ -358,13 +358,24 @@ class DgsSamplerStepArgs(ctypes.Structure):
                 ("clip_denoised", ctypes.c_int32), ("out", ctypes.c_void_p), ("pred_xstart", ctypes.c_void_p), ("bad_t", ctypes.c_void_p)]
 
 
+class DgsTrainInputsArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("V", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("clean_views", ctypes.c_int32),
+                ("image", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("noise_stride", ctypes.c_int64), ("noise_offset", ctypes.c_int64), ("t", ctypes.c_void_p),
+                ("sqrt_acp", ctypes.c_void_p), ("sqrt_1m_acp", ctypes.c_void_p), ("T", ctypes.c_int32), ("out_image", ctypes.c_void_p),
+                ("depth", ctypes.c_void_p), ("ray_o", ctypes.c_void_p), ("ray_d", ctypes.c_void_p), ("out_gt_xyz", ctypes.c_void_p),
+                ("bad_t", ctypes.c_void_p)]
+
+
 # every symbol include/dgs_sampler.h declares (checked by tests/test_abi.py)
-SAMPLER_SYMBOLS = ["dgs_sampler_step"]
+SAMPLER_SYMBOLS = ["dgs_sampler_step", "dgs_train_inputs"]
 
 
 def _declare_sampler(L):
     L.dgs_sampler_step.restype = ctypes.c_int
     L.dgs_sampler_step.argtypes = [ctypes.POINTER(DgsSamplerStepArgs), ctypes.c_void_p]
+    if hasattr(L, "dgs_train_inputs"):                    # absent from a build that predates the training inputs (an A/B side): sampler.py refuses them there
+        L.dgs_train_inputs.restype = ctypes.c_int
+        L.dgs_train_inputs.argtypes = [ctypes.POINTER(DgsTrainInputsArgs), ctypes.c_void_p]
     return L
 
 
@@ -386,7 +397,7 @@ class DgsPointsLossArgs(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("V", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("aligned", ctypes.c_void_p),
                 ("ray_o", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("masks", ctypes.c_void_p), ("pointsdist", ctypes.c_void_p),
                 ("xyz", ctypes.c_void_p), ("w_pointsdist", ctypes.c_void_p), ("w_xyz", ctypes.c_float), ("grad", ctypes.c_void_p),
-                ("workspace", ctypes.c_void_p)]
+                ("workspace", ctypes.c_void_p), ("xyz_denominator", ctypes.c_void_p), ("w_xyz_dev", ctypes.c_void_p)]
 
 
 class DgsSsimArgs(ctypes.Structure):

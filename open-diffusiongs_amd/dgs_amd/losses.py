@@ -1,6 +1,6 @@
 """Loss consumers on the device: per-sample MSE + PSNR and the MSE gradient in one pass, the SSIM
 term fused with them, the LPIPS input resize, and the two terms on the denoiser's pixel-aligned points (points-distribution and xyz
-loss) with their gradient.
+loss) with their gradient, and the reference's weight schedules (`scheduled_weight`).
 
 Mirrors diffusionGS/utils/losses.py: the `l2_loss` / `psnr` terms of LossComputer.forward (:281-285, :303), `compute_psnr`
 (:399-402), `SsimLoss` (:216-234, :317-321), `l2_loss_xyz` (:288-292) and `pointsdist_loss` (:325-364).  The LPIPS network (VGG,
@@ -107,7 +107,7 @@ def lpips_input(images, size=(256, 256), lib=None):
     return _LpipsInput.apply(images, tuple(size), 2.0, -1.0, lib)
 
 
-def _points_call(aligned, ray_o, gt, masks, w_pd, w_xyz, want_grad, lib):
+def _points_call(aligned, ray_o, gt, masks, w_pd, w_xyz, want_grad, lib, denominator=None, w_xyz_dev=None):
     B, V, C, H, W = aligned.shape
     assert C == 3 and ray_o.shape == aligned.shape
     dev = aligned.device
@@ -126,6 +126,11 @@ def _points_call(aligned, ray_o, gt, masks, w_pd, w_xyz, want_grad, lib):
     a.B, a.V, a.H, a.W = B, V, H, W
     a.aligned, a.ray_o, a.gt, a.masks, a.pointsdist, a.xyz = ptr(al), ptr(ro), ptr(gt), ptr(masks), ptr(pd), ptr(xyz)
     a.w_pointsdist, a.w_xyz, a.grad, a.workspace = ptr(wpd), float(w_xyz), ptr(grad), ptr(ws)
+    if denominator is not None or w_xyz_dev is not None:
+        if not hasattr(L, "dgs_train_inputs"):         # the two fields came with that symbol: an older build would silently ignore them
+            raise RuntimeError("dgs_amd: this library build predates DgsPointsLossArgs.xyz_denominator -- rebuild it (`python -m dgs_amd.build`)")
+        denominator, w_xyz_dev = f(denominator), f(w_xyz_dev)
+        a.xyz_denominator, a.w_xyz_dev = ptr(denominator), ptr(w_xyz_dev)
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if al.is_cuda else None
     rc = L.dgs_points_loss(ctypes.byref(a), stream)
     if rc != 0:
@@ -156,6 +161,59 @@ def points_losses(img_aligned_xyz, ray_o, gt_img_aligned_xyz=None, masks=None, l
     w.r.t. `img_aligned_xyz` [b, v, 3, h, w] (the statistics of the points-distribution target are detached, as in the reference).
     `masks` [b, v, 1, h, w] is the reference's `masks_input`."""
     return _PointsLoss.apply(img_aligned_xyz, ray_o, gt_img_aligned_xyz, masks, lib)
+
+
+class _PointsLossPart(torch.autograd.Function):
+    """points_losses of a micro-batch whose xyz term is divided by a mask sum given on the device; the upstream gradient of xyz stays
+    on the device as well (DgsPointsLossArgs.xyz_denominator / w_xyz_dev): no host read in either direction."""
+
+    @staticmethod
+    def forward(ctx, aligned, ray_o, gt, masks, denominator, lib):
+        pd, xyz, _ = _points_call(aligned, ray_o, gt, masks, None, 0.0, False, lib, denominator=denominator)
+        ctx.save_for_backward(aligned, ray_o, gt, masks, denominator)
+        ctx.lib = lib
+        return pd, xyz
+
+    @staticmethod
+    def backward(ctx, g_pd, g_xyz):
+        aligned, ray_o, gt, masks, denominator = ctx.saved_tensors
+        dev = aligned.device
+        w_pd = g_pd if g_pd is not None else torch.zeros(aligned.shape[0], device=dev)
+        w_dev = g_xyz.reshape(1) if g_xyz is not None else torch.zeros(1, device=dev)
+        _, _, grad = _points_call(aligned, ray_o, gt, masks, w_pd, 1.0, True, ctx.lib, denominator=denominator, w_xyz_dev=w_dev)
+        return grad.to(aligned.dtype), None, None, None, None, None
+
+
+def points_losses_part(img_aligned_xyz, ray_o, gt_img_aligned_xyz, masks, mask_sum, lib=None):
+    """`points_losses` for a PART of a batch: -> (pointsdist_loss [b] of the part, sum((aligned m - gt m)^2) of the part / mask_sum).
+    `mask_sum` is a device float tensor of one element, the whole batch's `masks.sum()`: the parts' xyz terms then add up to the
+    reference's scalar (losses.py:288-292) and their gradients to its gradient.  Nothing is read back to the host."""
+    return _PointsLossPart.apply(img_aligned_xyz, ray_o, gt_img_aligned_xyz, masks, mask_sum.reshape(1), lib)
+
+
+def scheduled_weight(value, global_step, epoch=0):
+    """`C()` of the reference (utils/misc.py:73-94), which turns an entry of `system.loss` into the weight of this step: a number is
+    returned as it is; a list [start_step, start_value, end_value, end_step] (three values: start_step = 0) interpolates linearly
+    between the two values and clamps outside -- over optimizer steps when end_step is an int, over epochs when it is a float.
+    `lambda_pointsdist: [150, 1., 0., 151]` of configs/diffusionGS_rel.yaml is 1 up to step 150 and 0 from step 151."""
+    if isinstance(value, (int, float)):
+        return value
+    if isinstance(value, tuple) or type(value).__name__ == "ListConfig":      # config_to_primitive: an OmegaConf list is a list
+        value = list(value)
+    if not isinstance(value, list):
+        raise TypeError("Scalar specification only supports list, got", type(value))
+    if len(value) == 3:
+        value = [0] + value
+    if len(value) != 4:
+        raise ValueError(f"a schedule has 3 or 4 entries, got {len(value)}")
+    start_step, start_value, end_value, end_step = value
+    if isinstance(end_step, int):
+        current = global_step
+    elif isinstance(end_step, float):
+        current = epoch
+    else:
+        raise TypeError("Scalar specification: end_step is an int (steps) or a float (epochs), got", type(end_step))
+    return start_value + (end_value - start_value) * max(min(1.0, (current - start_step) / (end_step - start_step)), 0.0)
 
 
 SSIM_WINDOW = 11

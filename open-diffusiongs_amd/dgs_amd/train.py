@@ -1,5 +1,11 @@
 """One data-parallel training step of the hot path (what PointDiffusionSystem.training_step does around the model,
-systems/diffusion_gs_system.py:71-128, minus the parts that are out of scope: noise schedule, the LPIPS network, logging):
+systems/diffusion_gs_system.py:71-128, minus the parts that are out of scope: the LPIPS network's weights -- there is a slot for a
+network of the user's -- Lightning, logging back ends and data loading).
+
+`train_step(clean batch)` after `configure_objective(diffusion, loss, perceptual)` is the reference's step: the noise and timestep
+draws, q_sample and the xyz target (ONE launch, dgs_train_inputs), every loss term the library has on the device -- MSE, SSIM,
+points-distribution, xyz, the perceptual slot -- under the `[start_step, start_value, end_value, end_step]` weight schedules of the
+shipped configs.  `step(batch, t, target)` is the same loop on views somebody else noised, with the MSE (+ SSIM) term:
 
     gaussians = model.image_to_gaussians(noisy views)          DiT forward, activations saved / per-block recompute   (HIP)
     renders   = model.render_gaussians(gaussians, cameras)     all b*v views, one launch sequence                     (HIP)
@@ -107,6 +113,10 @@ class DataParallelTrainer:
         self.last_psnr = None
         self.last_ssim_loss = None       # [b] of the last micro-batch when lambda_ssim is set
         self.lead_probe = None           # a list: every block_done callback appends (stage, host time, event recorded on the compute stream)
+        self._objective = None           # configure_objective: (diffusion, {lambda_*: number | schedule}, perceptual)
+        self.global_step = 0             # calls of train_step (a plain int: set it when resuming); the schedules read it
+        self.epoch = 0                   # read by schedules whose end_step is a float (utils/misc.py:89-93); the caller advances it
+        self.last_terms = None           # train_step: {"loss_*": detached mean, "lambda_*": the weight used, "timesteps", "x_t", "loss"}
 
     def close(self):
         """Give the model back: no in-place gradients, no per-block hook; the parameters keep COPIES of their last gradients."""
@@ -166,19 +176,40 @@ class DataParallelTrainer:
             self._summed_to = end
         self.reducer.ready_up_to(end, tag=stage)
 
-    def step(self, batch, t, target, render_c2w=None, render_fxfycxcy=None):
-        """batch: dict(image, ray_o, ray_d, c2w, fxfycxcy) like the reference's input_batch (leading dim = accumulate *
-        per-micro-batch size when accumulate_grad_batches > 1); target [b, v, 3, H, W].  Returns the (local) mean loss."""
-        m, K = self.model, self.accumulate
+    def _check_open(self):
+        m = self.model
         if m._block_hook != self._on_gradients_final:
             raise RuntimeError("DataParallelTrainer.step after close() (or another trainer took the model over)")
         if getattr(m, "_ema_swapped", False):
             raise RuntimeError("DataParallelTrainer.step inside `evaluate()` / `ema.swapped(model)`: the engine holds the averaged weights")
-        self._attach_grads()
+
+    def step(self, batch, t, target, render_c2w=None, render_fxfycxcy=None):
+        """batch: dict(image, ray_o, ray_d, c2w, fxfycxcy) like the reference's input_batch (leading dim = accumulate *
+        per-micro-batch size when accumulate_grad_batches > 1); target [b, v, 3, H, W].  Returns the (local) mean loss."""
+        m = self.model
+        self._check_open()
         c2w = batch["c2w"] if render_c2w is None else render_c2w
         k = batch["fxfycxcy"] if render_fxfycxcy is None else render_fxfycxcy
-        H, W = batch["image"].shape[3], batch["image"].shape[4]
-        nb = batch["image"].shape[0]
+
+        def micro_loss(sl, rendered, _aligned, _K):
+            if self.lambda_ssim is None:
+                loss, _l2, self.last_psnr = losses.mse_psnr(rendered, target[sl].to(rendered.dtype), lib=getattr(m, "_lib", None))
+            else:
+                loss, _l2, self.last_psnr, ssim_term = losses.image_losses(rendered, target[sl].to(rendered.dtype), 1.0, self.lambda_ssim,
+                                                                            lib=getattr(m, "_lib", None))
+                self.last_ssim_loss = ssim_term.detach()
+            return loss
+
+        return self._optimizer_step(batch["image"], batch["ray_o"], batch["ray_d"], t, c2w, k, micro_loss)
+
+    def _optimizer_step(self, image, ray_o, ray_d, t, c2w, k, micro_loss):
+        """One optimizer step over the local batch, shared by `step` and `train_step`: micro-batches and accumulation, per micro-batch
+        the forward, the render, `micro_loss(slice, rendered, aligned, micro-batches) -> scalar` and its backward; then the all-reduce,
+        the clip, the update, the EMA and the refresh.  Returns the mean of the micro-batches' losses."""
+        m, K = self.model, self.accumulate
+        self._attach_grads()
+        H, W = image.shape[3], image.shape[4]
+        nb = image.shape[0]
         assert nb % K == 0, "batch size must be a multiple of accumulate_grad_batches"
         mb = nb // K
         limit = getattr(m, "MAX_DIFFERENTIABLE_BATCH", 4)
@@ -195,17 +226,13 @@ class DataParallelTrainer:
         total = 0.0
         self._summed_to = 0
         self._use_accum = K > 1
+        self._micro_batches = K
         for j in range(K):
             sl = slice(j * mb, (j + 1) * mb)
             self._last_micro = j == K - 1
-            params, _ = m.image_to_gaussians(batch["image"][sl], batch["ray_o"][sl], batch["ray_d"][sl], t[sl])
+            params, aligned = m.image_to_gaussians(image[sl], ray_o[sl], ray_d[sl], t[sl])
             rendered = m.render_gaussians(params, c2w[sl], k[sl], H, W)
-            if self.lambda_ssim is None:
-                loss, _l2, self.last_psnr = losses.mse_psnr(rendered, target[sl].to(rendered.dtype), lib=getattr(m, "_lib", None))
-            else:
-                loss, _l2, self.last_psnr, ssim_term = losses.image_losses(rendered, target[sl].to(rendered.dtype), 1.0, self.lambda_ssim,
-                                                                            lib=getattr(m, "_lib", None))
-                self.last_ssim_loss = ssim_term.detach()
+            loss = micro_loss(sl, rendered, aligned, K)
             (loss * (1.0 / (K * self.world))).backward()       # mean over micro-batches and ranks folded into the scale
             total = total + loss.detach()
             if not self._last_micro:
@@ -241,3 +268,119 @@ class DataParallelTrainer:
         else:
             m.refresh_engine_weights()
         return total / K
+
+    # ---- the reference's training objective from a clean batch (PointDiffusionSystem.forward + training_step) ----
+    LOSS_KEYS = ("lambda_diffusion", "lambda_lpips", "lambda_ssim", "lambda_pointsdist", "lambda_xyz")
+
+    def configure_objective(self, diffusion, loss, perceptual=None):
+        """diffusion: `dgs_amd.sampler.create_diffusion("1000")` (the reference's `diffusion_training`).
+        loss: a mapping with the reference's `system.loss` keys -- lambda_diffusion, lambda_lpips, lambda_ssim, lambda_pointsdist,
+        lambda_xyz -- each a number, a schedule list `[start_step, start_value, end_value, end_step]` (losses.scheduled_weight) or
+        None / absent.  None or absent: the term is neither evaluated nor logged.  A number, 0.0 included, is evaluated, logged in
+        `last_terms` and enters the sum with its weight, as in the reference.  lambda_depth must be 0 / None / absent: the reference's
+        depth loss is commented out (utils/losses.py:294-297).
+        perceptual: any callable (x, y) -> tensor on [n, 3, 256, 256] images in (-1, 1); `lpips.LPIPS(net="vgg")`, frozen and on the
+        model's device, goes here.  It sees `losses.lpips_input(rendered)` and `losses.lpips_input(target)` (the HIP resize), loss_lpips
+        is its `.mean()` (utils/losses.py:304-309) and its gradient reaches the renders through autograd.  The network itself is not
+        part of this library."""
+        loss = dict(loss)
+        if loss.get("lambda_depth") not in (None, 0, 0.0):
+            raise ValueError("lambda_depth: the reference's depth loss is commented out (utils/losses.py:294-297); there is no such term")
+        unknown = sorted(k for k in loss if k.startswith("lambda_") and k not in self.LOSS_KEYS + ("lambda_depth",))
+        if unknown:
+            raise ValueError(f"unknown loss terms {unknown}; the reference has {list(self.LOSS_KEYS)}")
+        lam = {k: loss.get(k) for k in self.LOSS_KEYS}
+        for k, v in lam.items():
+            if v is not None:
+                losses.scheduled_weight(v, 0)                                  # a TypeError now, not at step 0
+        if lam["lambda_lpips"] is not None and perceptual is None:
+            raise ValueError("lambda_lpips is set: pass the network as `perceptual` (e.g. lpips.LPIPS(net='vgg')); this library has none")
+        if all(v is None for v in lam.values()):
+            raise ValueError("configure_objective: every loss term is None")
+        if diffusion.num_timesteps != 1000:
+            raise ValueError(f"the reference trains on create_diffusion('1000'); this one has {diffusion.num_timesteps} steps")
+        self._objective = (diffusion, lam, perceptual)
+
+    def train_step(self, batch, noise=None, timesteps=None):
+        """PointDiffusionSystem.forward + training_step (systems/diffusion_gs_system.py:71-129) on the reference's CLEAN batch -- keys
+        rgbs_input, c2ws_input, fxfycxcys_input, depths_input, masks_input (the input views) and c2ws, fxfycxcys, rgbs, masks (all
+        rendered views) -- after `configure_objective`:
+            noise = randn_like(rgbs_input), then timesteps = randint(0, T, (b,)), on the batch's device: from one torch.manual_seed
+                the reference's draws (pass either to override)
+            rays of the input views                                             HIP: backend.rays_from_c2w
+            noisy views + gt_img_aligned_xyz = ray_o + ray_d * depths_input     HIP: ONE launch, diffusion.training_inputs
+            per micro-batch: forward, render, image terms (losses.image_losses / mse_psnr), point terms on `aligned`
+                (losses.points_losses), the perceptual slot; loss = sum_k scheduled_weight(lambda_k, global_step) * loss_k
+            the scaling, all-reduce, clip, optimizer step, EMA and refresh of `step` (the same loop)
+        The noisy views go into a fresh tensor: the caller's batch is NOT modified (the reference noises `batch['rgbs_input']` in place).
+        loss_xyz is one scalar for the local batch, sum / masks_input.sum(): a micro-batch divides its sum by the WHOLE local batch's
+        mask sum, on the device, so the gradient is that of the unsplit evaluation.  Afterwards `last_terms` holds what the reference
+        logs under train/ and train_params/ (detached device scalars `loss_*`, the weights used `lambda_*`) and what its forward returns
+        besides (`timesteps`, `x_t`, the weighted `loss`); `global_step` has advanced by one and
+        `diffusion.bad_t` is still 0 unless a given timestep was outside [0, T).  Returns the (local) weighted loss."""
+        if self._objective is None:
+            raise RuntimeError("DataParallelTrainer.train_step before configure_objective")
+        self._check_open()
+        diffusion, lam, perceptual = self._objective
+        m = self.model
+        lib = getattr(m, "_lib", None)
+        clean = batch["rgbs_input"]
+        b, _v, _c, H, W = clean.shape
+        if noise is None:
+            noise = torch.randn_like(clean)                                     # :77
+        if timesteps is None:
+            timesteps = torch.randint(0, diffusion.num_timesteps, (b,), device=clean.device)     # :79-85
+        timesteps = timesteps.long()
+        ray_o, ray_d = self._raster_backend.rays_from_c2w(batch["c2ws_input"], batch["fxfycxcys_input"], H, W)
+        want_xyz = lam["lambda_xyz"] is not None
+        x_t, gt_xyz = diffusion.training_inputs(clean, timesteps, noise, *((batch["depths_input"], ray_o, ray_d) if want_xyz else ()))
+        masks_in = batch["masks_input"].float() if want_xyz else None
+        mask_sum = masks_in.sum(dtype=torch.float64).float().reshape(1) if want_xyz else None      # stays on the device
+        w = {k: (None if v is None else float(losses.scheduled_weight(v, self.global_step, self.epoch))) for k, v in lam.items()}
+        target = batch["rgbs"]
+        sums = {}
+
+        def add(name, value):
+            sums[name] = sums[name] + value.detach() if name in sums else value.detach()
+
+        def micro_loss(sl, rendered, aligned, K):
+            tgt = target[sl].to(rendered.dtype)
+            parts = []
+            if w["lambda_ssim"] is not None:                                   # one fused node for both image terms, as in `step`
+                img, l2, self.last_psnr, ssim_term = losses.image_losses(rendered, tgt, w["lambda_diffusion"] or 0.0, w["lambda_ssim"], lib=lib)
+                self.last_ssim_loss = ssim_term.detach()
+                add("loss_ssim", ssim_term.mean())
+                if w["lambda_diffusion"] is not None:
+                    add("loss_diffusion", l2.mean())
+                parts.append(img)
+            elif w["lambda_diffusion"] is not None:
+                mse, _l2, self.last_psnr = losses.mse_psnr(rendered, tgt, lib=lib)
+                add("loss_diffusion", mse)
+                parts.append(mse * w["lambda_diffusion"])                    # weight 1.0: the bits of `step`
+            if want_xyz:
+                pd, xyz = losses.points_losses_part(aligned, ray_o[sl], gt_xyz[sl], masks_in[sl], mask_sum, lib=lib)
+                xyz = xyz * float(K)                   # the parts ADD up to the batch's scalar; the loop takes the MEAN over micro-batches
+                add("loss_xyz", xyz)
+                parts.append(xyz * w["lambda_xyz"])
+            elif w["lambda_pointsdist"] is not None:
+                pd, _ = losses.points_losses(aligned, ray_o[sl], lib=lib)
+            if w["lambda_pointsdist"] is not None:
+                pd = pd.mean()                                               # the system's `pointsdist_loss.mean()`, :109
+                add("loss_pointsdist", pd)
+                parts.append(pd * w["lambda_pointsdist"])
+            if w["lambda_lpips"] is not None:
+                flat = lambda x: x.reshape(-1, *x.shape[2:])
+                lp = perceptual(losses.lpips_input(flat(rendered), lib=lib), losses.lpips_input(flat(tgt), lib=lib)).mean()
+                add("loss_lpips", lp)
+                parts.append(lp * w["lambda_lpips"])
+            loss = parts[0]
+            for p in parts[1:]:
+                loss = loss + p
+            return loss
+
+        total = self._optimizer_step(x_t, ray_o, ray_d, timesteps, batch["c2ws"], batch["fxfycxcys"], micro_loss)
+        self.last_terms = {k: v / self._micro_batches for k, v in sums.items()}
+        self.last_terms.update({k: v for k, v in w.items() if v is not None})
+        self.last_terms.update(timesteps=timesteps, x_t=x_t, loss=total)
+        self.global_step += 1
+        return total
