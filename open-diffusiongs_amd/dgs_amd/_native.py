@@ -618,8 +618,60 @@ def _declare_mesh_smooth(L):
     return L
 
 
+class DgsConv3x3Args(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32),
+                ("x", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("relu", ctypes.c_int32), ("y", ctypes.c_void_p)]
+
+
+class DgsMaxPool2x2Args(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32), ("x", ctypes.c_void_p),
+                ("y", ctypes.c_void_p)]
+
+
+class DgsLpipsPackArgs(ctypes.Structure):
+    _fields_ = [("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32), ("w", ctypes.c_void_p), ("packed", ctypes.c_void_p)]
+
+
+class DgsLpipsTapArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32), ("f0", ctypes.c_void_p),
+                ("f1", ctypes.c_void_p), ("lin", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_stride", ctypes.c_int32),
+                ("workspace", ctypes.c_void_p)]
+
+
+LPIPS_CONVS, LPIPS_TAPS = 13, 5
+
+
+class DgsLpipsForwardArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("x0", ctypes.c_void_p), ("x1", ctypes.c_void_p),
+                ("shift", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("conv_w", ctypes.c_void_p * LPIPS_CONVS),
+                ("conv_b", ctypes.c_void_p * LPIPS_CONVS), ("lin", ctypes.c_void_p * LPIPS_TAPS), ("out", ctypes.c_void_p),
+                ("per_tap", ctypes.c_void_p), ("features", ctypes.POINTER(ctypes.c_void_p)), ("chunk", ctypes.c_int32),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+# every symbol include/dgs_lpips.h declares (checked by tests/test_lpips_emu.py)
+LPIPS_SYMBOLS = ["dgs_conv3x3_packed_floats", "dgs_lpips_pack_weights", "dgs_conv3x3", "dgs_maxpool2x2", "dgs_lpips_tap", "dgs_lpips_chunk",
+                 "dgs_lpips_workspace_bytes", "dgs_lpips_forward"]
+
+
+def _declare_lpips(L):
+    if not all(hasattr(L, name) for name in LPIPS_SYMBOLS):              # a build that predates the LPIPS network (an A/B side): lpips.py refuses it there
+        return L
+    L.dgs_conv3x3_packed_floats.restype = ctypes.c_int64
+    L.dgs_conv3x3_packed_floats.argtypes = [ctypes.c_int32, ctypes.c_int32]
+    for name, argt in (("dgs_lpips_pack_weights", DgsLpipsPackArgs), ("dgs_conv3x3", DgsConv3x3Args), ("dgs_maxpool2x2", DgsMaxPool2x2Args),
+                       ("dgs_lpips_tap", DgsLpipsTapArgs), ("dgs_lpips_forward", DgsLpipsForwardArgs)):
+        getattr(L, name).restype = ctypes.c_int
+        getattr(L, name).argtypes = [ctypes.POINTER(argt), ctypes.c_void_p]
+    L.dgs_lpips_chunk.restype = ctypes.c_int32
+    L.dgs_lpips_chunk.argtypes = [ctypes.c_int32] * 3
+    L.dgs_lpips_workspace_bytes.restype = ctypes.c_size_t
+    L.dgs_lpips_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+    return L
+
+
 _declare_raster = _declare
 
 
-def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up + decimation + attributes + smoothing prototypes on one library)
-    return _declare_mesh_smooth(_declare_mesh_attr(_declare_mesh_decimate(_declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L))))))))))))
+def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up + decimation + attributes + smoothing + LPIPS prototypes on one library)
+    return _declare_lpips(_declare_mesh_smooth(_declare_mesh_attr(_declare_mesh_decimate(_declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L)))))))))))))
