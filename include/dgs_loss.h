@@ -7,9 +7,9 @@
  *     compute_psnr: clamp both to [0, 1] first                                                               :399-402
  * and the autograd backward of the lambda_mse term (d/d rendering = 2 (rendering - target) * grad_scale / n).
  * and the SSIM term (`SsimLoss`, :216-234; evaluated over all b * v views on every step, :317-321): DgsSsimArgs below.
- * The LPIPS network's forward is include/dgs_lpips.h (csrc/lpips.hip; the metric of MetricComputer).  It has no input gradient yet, so
- * the LPIPS TERM of the loss is not here: its input path is DgsResizeArgs, and the trainer has a slot for a differentiable network
- * supplied by the user (DataParallelTrainer.configure_objective(perceptual=...)).  One pass over the images, per-sample
+ * The LPIPS network, forward and input gradient, is include/dgs_lpips.h (csrc/lpips.hip; the metric of MetricComputer and the
+ * LPIPS TERM of the loss): its input path is DgsResizeArgs here, and the trainer's slot takes it or any differentiable network
+ * (DataParallelTrainer.configure_objective(perceptual=...)).  One pass over the images, per-sample
  * sums reduced in a fixed order (deterministic), no host synchronisation.  Device pointers; returns DGS_OK or a negative DgsStatus.
  */
 #ifndef DGS_LOSS_H
@@ -43,7 +43,7 @@ int dgs_mse_psnr(const DgsMseArgs* args, dgs_stream_t stream);
 /* The input path of the LPIPS term (losses.py:304-309): `F.interpolate(x, size=[256, 256], mode='bilinear') * 2.0 - 1.0`
  * for renderings and targets -- evaluated every step, also when lambda_lpips is 0.  One launch: bilinear resize
  * (align_corners = False, PyTorch's source-index rule) fused with the affine map; the backward accumulates
- * d src = mul * W^T d dst (dsrc is zero-filled by the call).  The network behind it: include/dgs_lpips.h (forward only). */
+ * d src = mul * W^T d dst (dsrc is zero-filled by the call).  The network behind it: include/dgs_lpips.h. */
 typedef struct DgsResizeArgs {
     int32_t planes;            /* n * c image planes                                                       */
     int32_t in_h, in_w, out_h, out_w;

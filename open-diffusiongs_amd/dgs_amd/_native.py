@@ -649,24 +649,60 @@ class DgsLpipsForwardArgs(ctypes.Structure):
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+class DgsConv3x3BackwardDataArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32),
+                ("dy", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("add", ctypes.c_void_p),
+                ("dx", ctypes.c_void_p)]
+
+
+class DgsMaxPool2x2BackwardArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32), ("x", ctypes.c_void_p),
+                ("dy", ctypes.c_void_p), ("relu_mask", ctypes.c_int32), ("add", ctypes.c_void_p), ("dx", ctypes.c_void_p)]
+
+
+class DgsLpipsTapBackwardArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32), ("f0", ctypes.c_void_p),
+                ("f1", ctypes.c_void_p), ("lin", ctypes.c_void_p), ("g0", ctypes.c_void_p), ("g1", ctypes.c_void_p)]
+
+
+class DgsLpipsGradArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("x0", ctypes.c_void_p), ("x1", ctypes.c_void_p),
+                ("shift", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("conv_w", ctypes.c_void_p * LPIPS_CONVS),
+                ("conv_wt", ctypes.c_void_p * LPIPS_CONVS), ("conv_b", ctypes.c_void_p * LPIPS_CONVS),
+                ("lin", ctypes.c_void_p * LPIPS_TAPS), ("out", ctypes.c_void_p), ("per_tap", ctypes.c_void_p), ("grad0", ctypes.c_void_p),
+                ("grad1", ctypes.c_void_p), ("chunk", ctypes.c_int32), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 # every symbol include/dgs_lpips.h declares (checked by tests/test_lpips_emu.py)
 LPIPS_SYMBOLS = ["dgs_conv3x3_packed_floats", "dgs_lpips_pack_weights", "dgs_conv3x3", "dgs_maxpool2x2", "dgs_lpips_tap", "dgs_lpips_chunk",
-                 "dgs_lpips_workspace_bytes", "dgs_lpips_forward"]
+                 "dgs_lpips_workspace_bytes", "dgs_lpips_forward", "dgs_lpips_pack_weights_transposed", "dgs_conv3x3_backward_data",
+                 "dgs_maxpool2x2_backward", "dgs_lpips_tap_backward", "dgs_lpips_grad_chunk", "dgs_lpips_grad_workspace_bytes",
+                 "dgs_lpips_forward_backward"]
 
 
 def _declare_lpips(L):
-    if not all(hasattr(L, name) for name in LPIPS_SYMBOLS):              # a build that predates the LPIPS network (an A/B side): lpips.py refuses it there
+    if not all(hasattr(L, name) for name in LPIPS_SYMBOLS[:8]):          # a build that predates the LPIPS network (an A/B side): lpips.py refuses it there
         return L
     L.dgs_conv3x3_packed_floats.restype = ctypes.c_int64
     L.dgs_conv3x3_packed_floats.argtypes = [ctypes.c_int32, ctypes.c_int32]
-    for name, argt in (("dgs_lpips_pack_weights", DgsLpipsPackArgs), ("dgs_conv3x3", DgsConv3x3Args), ("dgs_maxpool2x2", DgsMaxPool2x2Args),
-                       ("dgs_lpips_tap", DgsLpipsTapArgs), ("dgs_lpips_forward", DgsLpipsForwardArgs)):
+    protos = [("dgs_lpips_pack_weights", DgsLpipsPackArgs), ("dgs_conv3x3", DgsConv3x3Args), ("dgs_maxpool2x2", DgsMaxPool2x2Args),
+              ("dgs_lpips_tap", DgsLpipsTapArgs), ("dgs_lpips_forward", DgsLpipsForwardArgs)]
+    sizes, counts = ["dgs_lpips_workspace_bytes"], ["dgs_lpips_chunk"]
+    if all(hasattr(L, name) for name in LPIPS_SYMBOLS[8:]):              # the input gradient; a forward-only build (an A/B side) keeps the metric
+        protos += [("dgs_lpips_pack_weights_transposed", DgsLpipsPackArgs), ("dgs_conv3x3_backward_data", DgsConv3x3BackwardDataArgs),
+                   ("dgs_maxpool2x2_backward", DgsMaxPool2x2BackwardArgs), ("dgs_lpips_tap_backward", DgsLpipsTapBackwardArgs),
+                   ("dgs_lpips_forward_backward", DgsLpipsGradArgs)]
+        sizes.append("dgs_lpips_grad_workspace_bytes")
+        counts.append("dgs_lpips_grad_chunk")
+    for name, argt in protos:
         getattr(L, name).restype = ctypes.c_int
         getattr(L, name).argtypes = [ctypes.POINTER(argt), ctypes.c_void_p]
-    L.dgs_lpips_chunk.restype = ctypes.c_int32
-    L.dgs_lpips_chunk.argtypes = [ctypes.c_int32] * 3
-    L.dgs_lpips_workspace_bytes.restype = ctypes.c_size_t
-    L.dgs_lpips_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+    for name in counts:
+        getattr(L, name).restype = ctypes.c_int32
+        getattr(L, name).argtypes = [ctypes.c_int32] * 3
+    for name in sizes:
+        getattr(L, name).restype = ctypes.c_size_t
+        getattr(L, name).argtypes = [ctypes.c_int32] * 3
     return L
 
 

@@ -3,8 +3,8 @@ term fused with them, the LPIPS input resize, and the two terms on the denoiser'
 loss) with their gradient, and the reference's weight schedules (`scheduled_weight`).
 
 Mirrors diffusionGS/utils/losses.py: the `l2_loss` / `psnr` terms of LossComputer.forward (:281-285, :303), `compute_psnr`
-(:399-402), `SsimLoss` (:216-234, :317-321), `l2_loss_xyz` (:288-292) and `pointsdist_loss` (:325-364).  The LPIPS network's forward
-is dgs_amd.lpips (no input gradient yet: a metric, not a loss term); MetricComputer (:373-473), its compute_ssim included, is
+(:399-402), `SsimLoss` (:216-234, :317-321), `l2_loss_xyz` (:288-292) and `pointsdist_loss` (:325-364).  The LPIPS network is
+dgs_amd.lpips (the metric, and with differentiable=True the loss term with its input gradient); MetricComputer (:373-473), its compute_ssim included, is
 dgs_amd.metrics, which says how skimage's operator relates to `ssim` here.
 csrc/loss.hip and csrc/ssim.hip through include/dgs_loss.h; no CPU fallback."""
 import ctypes
@@ -104,7 +104,7 @@ class _LpipsInput(torch.autograd.Function):
 def lpips_input(images, size=(256, 256), lib=None):
     """losses.py:304-309: `F.interpolate(images, size=[256, 256], mode='bilinear') * 2.0 - 1.0` -- what the reference feeds its
     LPIPS module for renderings and targets ([n, 3, h, w] in (0, 1) -> [n, 3, 256, 256] in (-1, 1)), one fused launch,
-    differentiable.  The network behind it is dgs_amd.lpips.LPIPS (forward only, so far)."""
+    differentiable.  The network behind it is dgs_amd.lpips.LPIPS (differentiable=True for a loss term)."""
     return _LpipsInput.apply(images, tuple(size), 2.0, -1.0, lib)
 
 

@@ -1,7 +1,10 @@
 """LPIPS-VGG on the device: what `lpips.LPIPS(net="vgg")` (version 0.1, lpips=True, spatial=False, eval mode) returns for two image
 batches, computed by csrc/lpips.hip through include/dgs_lpips.h (which states the network and its arithmetic) -- in fp32, as
 eval_scene_result.py of the reference runs it (no autocast), deterministically, with neither the `lpips` nor the `torchvision`
-package behind it.  FORWARD ONLY: there is no input gradient yet, so this is the metric (dgs_amd.metrics), not the trainer's term.
+package behind it.  The default module is the metric (dgs_amd.metrics) and refuses an input that requires grad;
+`LPIPS(..., differentiable=True)` is the trainer's perceptual term: its forward computes the gradient of every out[n] with respect to
+the images in the same call (dgs_lpips_forward_backward) and stores it, so no activation outlives the call and memory is bounded by
+the chunk, not by the batch.  The network is frozen: there is no weight gradient.
 
 State dict.  Parameters and buffers carry the names of the `lpips` package, so `load_state_dict(lpips.LPIPS(net="vgg").state_dict())`
 works strictly:
@@ -40,6 +43,13 @@ def _library(lib):
     return L
 
 
+def _gradient_library(lib):
+    L = _library(lib)
+    if not hasattr(L, "dgs_lpips_forward_backward"):
+        raise RuntimeError("dgs_amd: this library build predates the LPIPS input gradient -- rebuild it (`python -m dgs_amd.build`)")
+    return L
+
+
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -64,6 +74,62 @@ def pack_weights(weight, lib=None):
     a = _native.DgsLpipsPackArgs(cin, cout, _ptr(w), _ptr(packed))
     _check(L.dgs_lpips_pack_weights(ctypes.byref(a), _stream(w)), "dgs_lpips_pack_weights")
     return packed
+
+
+def pack_weights_transposed(weight, lib=None):
+    """[Cout, Cin, 3, 3] -> the packed operand of dgs_conv3x3_backward_data: the convolution Cout -> Cin on the flipped, transposed
+    weights, written straight from `weight`."""
+    L = _gradient_library(lib)
+    w = weight.detach().contiguous().float()
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    if tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"pack_weights_transposed: a [Cout, Cin, 3, 3] tensor expected, got {tuple(weight.shape)}")
+    packed = torch.empty(int(L.dgs_conv3x3_packed_floats(cout, cin)), dtype=torch.float32, device=w.device)
+    a = _native.DgsLpipsPackArgs(cin, cout, _ptr(w), _ptr(packed))
+    _check(L.dgs_lpips_pack_weights_transposed(ctypes.byref(a), _stream(w)), "dgs_lpips_pack_weights_transposed")
+    return packed
+
+
+def conv3x3_backward_data(dy, packed_t, cin, mask=None, add=None, lib=None):
+    """dy f32 [N, H, W, Cout] channels-last, packed_t = pack_weights_transposed(w) -> dx [N, H, W, cin] = (mask > 0 ? sum : 0) + add."""
+    L = _gradient_library(lib)
+    dy = dy.contiguous()
+    n, h, w, cout = (int(d) for d in dy.shape)
+    mask = mask.contiguous() if mask is not None else None
+    add = add.contiguous() if add is not None else None
+    assert all(t is None or tuple(t.shape) == (n, h, w, cin) for t in (mask, add))
+    dx = torch.empty(n, h, w, cin, dtype=torch.float32, device=dy.device)
+    a = _native.DgsConv3x3BackwardDataArgs(n, h, w, cin, cout, _ptr(dy), _ptr(packed_t), _ptr(mask), _ptr(add), _ptr(dx))
+    _check(L.dgs_conv3x3_backward_data(ctypes.byref(a), _stream(dy)), "dgs_conv3x3_backward_data")
+    return dx
+
+
+def maxpool2x2_backward(x, dy, relu_mask=False, add=None, lib=None):
+    """x f32 [N, H, W, C] (the pool's input), dy [N, H // 2, W // 2, C] -> dx [N, H, W, C]: dy routed to the first maximum of each
+    window, then (x > 0 ? . : 0) with relu_mask, then + add."""
+    L = _gradient_library(lib)
+    x, dy = x.contiguous(), dy.contiguous()
+    n, h, w, c = (int(d) for d in x.shape)
+    assert tuple(dy.shape) == (n, h // 2, w // 2, c)
+    add = add.contiguous() if add is not None else None
+    assert add is None or add.shape == x.shape
+    dx = torch.empty_like(x)
+    a = _native.DgsMaxPool2x2BackwardArgs(n, h, w, c, _ptr(x), _ptr(dy), int(relu_mask), _ptr(add), _ptr(dx))
+    _check(L.dgs_maxpool2x2_backward(ctypes.byref(a), _stream(x)), "dgs_maxpool2x2_backward")
+    return dx
+
+
+def tap_backward(f0, f1, lin, want_g1=True, lib=None):
+    """The gradient of tap_distance(f0, f1, lin)[n] with respect to f0 (and f1) -> (g0, g1 or None), 0 where the feature itself is 0."""
+    L = _gradient_library(lib)
+    f0, f1, lin = f0.contiguous(), f1.contiguous(), lin.contiguous().reshape(-1)
+    n, h, w, c = (int(d) for d in f0.shape)
+    assert f1.shape == f0.shape and lin.numel() == c
+    g0 = torch.empty_like(f0)
+    g1 = torch.empty_like(f1) if want_g1 else None
+    a = _native.DgsLpipsTapBackwardArgs(n, h, w, c, _ptr(f0), _ptr(f1), _ptr(lin), _ptr(g0), _ptr(g1))
+    _check(L.dgs_lpips_tap_backward(ctypes.byref(a), _stream(f0)), "dgs_lpips_tap_backward")
+    return g0, g1
 
 
 def conv3x3(x, packed, bias, cout, relu=True, lib=None):
@@ -123,16 +189,52 @@ class _Lin(nn.Module):
         self.weight = nn.Parameter(torch.zeros(1, c, 1, 1), requires_grad=False)
 
 
+class _LpipsFunction(torch.autograd.Function):
+    """out [n] with the gradient of out[n] with respect to the inputs that require grad computed in the forward call and stored (the
+    size of those inputs); backward multiplies the stored rows by grad_out[n].  Once differentiable: a second derivative raises."""
+
+    @staticmethod
+    def forward(ctx, module, in0, in1, chunk):
+        need0, need1 = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        swap = need1 and not need0            # the library's first image set is the one that always gets a gradient
+        r = module.run_with_gradient(in1 if swap else in0, in0 if swap else in1, both=need0 and need1, chunk=chunk)
+        g0, g1 = (r["grad1"], r["grad0"]) if swap else (r["grad0"], r["grad1"])
+        ctx.dtypes = (in0.dtype, in1.dtype)
+        ctx.devices = (in0.device, in1.device)
+        ctx.save_for_backward(*[g for g in (g0, g1) if g is not None])
+        ctx.which = (g0 is not None, g1 is not None)
+        return r["out"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        saved = list(ctx.saved_tensors)
+        grads = []
+        for i, have in enumerate(ctx.which):
+            if not have:
+                grads.append(None)
+                continue
+            g = saved.pop(0)
+            grads.append((grad_out.to(g.device, g.dtype).reshape(-1, 1, 1, 1) * g).to(ctx.devices[i], ctx.dtypes[i]))
+        return None, grads[0], grads[1], None
+
+
 class LPIPS(nn.Module):
     """`LPIPS(net="vgg")`: forward(in0, in1, normalize=False) -> [n, 1, 1, 1] for in0, in1 f32 [n, 3, H, W] in (-1, 1) (in (0, 1)
     with normalize=True), H, W >= 16.  `weights`: a state dict with the package's names, or a path to one.  The module holds no
-    weights of its own: until some are loaded, forward raises."""
+    weights of its own: until some are loaded, forward raises.
 
-    def __init__(self, net="vgg", weights=None, lib=None):
+    differentiable=False (the default): the metric; an input that requires grad (with grad enabled) raises NotImplementedError.
+    differentiable=True: such an input goes through one fused forward-and-backward call (dgs_lpips_forward_backward) that returns the
+    same bytes as the metric and stores d out[n] / d input for the inputs that require grad (a target that does not costs no backward
+    convolution); no activation outlives the call.  Under no_grad, or when no input requires grad, the metric's path runs."""
+
+    def __init__(self, net="vgg", weights=None, lib=None, differentiable=False):
         super().__init__()
         if net != "vgg":
             raise ValueError(f"dgs_amd.lpips.LPIPS: only net='vgg' is built (asked for {net!r}); 'alex' and 'squeeze' are not")
         self._lib = lib
+        self.differentiable = bool(differentiable)
         self.scaling_layer = _Holder()
         self.scaling_layer.register_buffer("shift", torch.tensor(SHIFT, dtype=torch.float32).reshape(1, 3, 1, 1))
         self.scaling_layer.register_buffer("scale", torch.tensor(SCALE, dtype=torch.float32).reshape(1, 3, 1, 1))
@@ -156,7 +258,7 @@ class LPIPS(nn.Module):
             self.load_state_dict(weights, strict=True)
 
     @classmethod
-    def from_files(cls, vgg16, lin, lib=None):
+    def from_files(cls, vgg16, lin, lib=None, differentiable=False):
         """vgg16: torchvision's `vgg16` state dict (or a path to it), of which `features.{0,2,...,28}.{weight,bias}` are read;
         lin: the package's `vgg.pth` (or a path), `lin{k}.model.1.weight`."""
         load = lambda x: x if isinstance(x, dict) else torch.load(x, map_location="cpu")
@@ -168,7 +270,7 @@ class LPIPS(nn.Module):
                 sd[f"net.{name}.{leaf}"] = vgg16[f"features.{i}.{leaf}"]
         for k in range(len(TAP_CHANNELS)):
             sd[f"lin{k}.model.1.weight"] = lin[f"lin{k}.model.1.weight"]
-        m = cls(net="vgg", lib=lib)
+        m = cls(net="vgg", lib=lib, differentiable=differentiable)
         sd["scaling_layer.shift"], sd["scaling_layer.scale"] = m.scaling_layer.shift, m.scaling_layer.scale
         m.load_state_dict(sd, strict=True)
         return m
@@ -192,29 +294,25 @@ class LPIPS(nn.Module):
     def lin_parameters(self):
         return [getattr(getattr(self, f"lin{k}").model, "1").weight for k in range(len(TAP_CHANNELS))]
 
-    def packed(self):
+    def packed(self, transposed=False):
         """The device-side operands (packed convolution weights, biases, lin vectors, shift and scale); rebuilt when a parameter's
-        version, storage or device changes (load_state_dict, .to(), an in-place update)."""
+        version, storage or device changes (load_state_dict, .to(), an in-place update).  transposed=True adds the operands of the data
+        gradient (`conv_wt`) to the same cache the first time the gradient is asked for; they are invalidated with the rest."""
         tensors = list(self.parameters()) + list(self.buffers())
         version = tuple((p._version, p.data_ptr(), str(p.device), p.dtype) for p in tensors)
         if self._packed is None or version != self._packed_version:
             f = lambda t: t.detach().float().contiguous().reshape(-1)
-            self._packed = dict(conv_w=[pack_weights(w, self._lib) for w, _ in self.conv_parameters()],
+            self._packed = dict(conv_w=[pack_weights(w, self._lib) for w, _ in self.conv_parameters()], conv_wt=None,
                                 conv_b=[f(b) for _, b in self.conv_parameters()], lin=[f(w) for w in self.lin_parameters()],
                                 shift=f(self.scaling_layer.shift), scale=f(self.scaling_layer.scale))
             self._packed_version = version
+        if transposed and self._packed["conv_wt"] is None:
+            self._packed["conv_wt"] = [pack_weights_transposed(w, self._lib) for w, _ in self.conv_parameters()]
         return self._packed
 
     def run(self, in0, in1, chunk=0, want_taps=False, want_features=False):
         """-> dict(out [n], per_tap [n, 5] or None, features: five [2, n, h_k, w_k, C_k] channels-last tensors or None)."""
-        if not self._loaded:
-            raise RuntimeError("dgs_amd.lpips.LPIPS: no weights have been loaded (load_state_dict, `weights=` or LPIPS.from_files); the "
-                               "library ships none")
-        if in0.shape != in1.shape or in0.dim() != 4 or in0.shape[1] != 3:
-            raise ValueError(f"LPIPS: two [n, 3, H, W] tensors of one shape expected, got {tuple(in0.shape)} and {tuple(in1.shape)}")
-        n, _, h, w = (int(d) for d in in0.shape)
-        if h < 16 or w < 16:
-            raise ValueError(f"LPIPS: images of {h} x {w} are smaller than 16 x 16, the last tap would be empty")
+        n, h, w = self._checked(in0, in1)
         L = _library(self._lib)
         dev = self.scaling_layer.shift.device
         x0, x1 = in0.detach().to(dev, torch.float32).contiguous(), in1.detach().to(dev, torch.float32).contiguous()
@@ -242,10 +340,58 @@ class LPIPS(nn.Module):
         _check(L.dgs_lpips_forward(ctypes.byref(a), _stream(x0)), "dgs_lpips_forward")
         return dict(out=out, per_tap=per_tap, features=feats)
 
+    def _checked(self, in0, in1):
+        if not self._loaded:
+            raise RuntimeError("dgs_amd.lpips.LPIPS: no weights have been loaded (load_state_dict, `weights=` or LPIPS.from_files); the "
+                               "library ships none")
+        if in0.shape != in1.shape or in0.dim() != 4 or in0.shape[1] != 3:
+            raise ValueError(f"LPIPS: two [n, 3, H, W] tensors of one shape expected, got {tuple(in0.shape)} and {tuple(in1.shape)}")
+        n, _, h, w = (int(d) for d in in0.shape)
+        if h < 16 or w < 16:
+            raise ValueError(f"LPIPS: images of {h} x {w} are smaller than 16 x 16, the last tap would be empty")
+        return n, h, w
+
+    def run_with_gradient(self, in0, in1, both=True, chunk=0, want_taps=False):
+        """One dgs_lpips_forward_backward call -> dict(out [n], per_tap [n, 5] or None, grad0 [n, 3, H, W] = d out[n] / d in0[n],
+        grad1 likewise or None when both is False).  Nothing here is recorded by autograd."""
+        n, h, w = self._checked(in0, in1)
+        L = _gradient_library(self._lib)
+        dev = self.scaling_layer.shift.device
+        x0, x1 = in0.detach().to(dev, torch.float32).contiguous(), in1.detach().to(dev, torch.float32).contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        grad0 = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
+        grad1 = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev) if both else None
+        per_tap = torch.empty(n, _native.LPIPS_TAPS, dtype=torch.float32, device=dev) if want_taps else None
+        if n == 0:
+            return dict(out=out, per_tap=per_tap, grad0=grad0, grad1=grad1)
+        pk = self.packed(transposed=True)
+        nbytes = int(L.dgs_lpips_grad_workspace_bytes(n, h, w))
+        if nbytes == 0:
+            raise ValueError(f"LPIPS: unsupported size n = {n}, {h} x {w}")
+        if chunk:
+            nbytes = int(L.dgs_lpips_grad_workspace_bytes(min(n, int(chunk)), h, w))
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        a = _native.DgsLpipsGradArgs()
+        a.N, a.H, a.W, a.x0, a.x1, a.shift, a.scale = n, h, w, _ptr(x0), _ptr(x1), _ptr(pk["shift"]), _ptr(pk["scale"])
+        for i in range(_native.LPIPS_CONVS):
+            a.conv_w[i], a.conv_wt[i], a.conv_b[i] = pk["conv_w"][i].data_ptr(), pk["conv_wt"][i].data_ptr(), pk["conv_b"][i].data_ptr()
+        for k in range(_native.LPIPS_TAPS):
+            a.lin[k] = pk["lin"][k].data_ptr()
+        a.out, a.per_tap, a.grad0, a.grad1 = _ptr(out), _ptr(per_tap), _ptr(grad0), _ptr(grad1)
+        a.chunk, a.workspace, a.workspace_bytes = int(chunk), _ptr(ws), nbytes
+        _check(L.dgs_lpips_forward_backward(ctypes.byref(a), _stream(x0)), "dgs_lpips_forward_backward")
+        return dict(out=out, per_tap=per_tap, grad0=grad0, grad1=grad1)
+
     def forward(self, in0, in1, normalize=False):
         if torch.is_grad_enabled() and (in0.requires_grad or in1.requires_grad):
-            raise NotImplementedError("dgs_amd.lpips.LPIPS has no input gradient yet (the convolution's data gradient is not built): call it "
-                                      "under torch.no_grad() as a metric; it cannot be a term of a loss")
+            if not self.differentiable:
+                raise NotImplementedError("dgs_amd.lpips.LPIPS(differentiable=False) is the metric and computes no input gradient: call it "
+                                          "under torch.no_grad(), or construct the module with differentiable=True to use it as a term of "
+                                          "a loss")
+            if normalize:
+                in0, in1 = 2 * in0 - 1, 2 * in1 - 1
+            self._checked(in0, in1)
+            return _LpipsFunction.apply(self, in0, in1, 0).reshape(-1, 1, 1, 1)
         if normalize:
             in0, in1 = 2 * in0 - 1, 2 * in1 - 1
         return self.run(in0, in1)["out"].reshape(-1, 1, 1, 1)

@@ -1,6 +1,6 @@
 """One data-parallel training step of the hot path (what PointDiffusionSystem.training_step does around the model,
-systems/diffusion_gs_system.py:71-128, minus the parts that are out of scope: the LPIPS network's weights -- there is a slot for a
-network of the user's -- Lightning, logging back ends and data loading).
+systems/diffusion_gs_system.py:71-128, minus the parts that are out of scope: the LPIPS network's weights -- the slot takes dgs_amd.lpips.LPIPS(differentiable=True) with
+weights of the user's, or any network -- Lightning, logging back ends and data loading).
 
 `train_step(clean batch)` after `configure_objective(diffusion, loss, perceptual)` is the reference's step: the noise and timestep
 draws, q_sample and the xyz target (ONE launch, dgs_train_inputs), every loss term the library has on the device -- MSE, SSIM,
@@ -279,10 +279,11 @@ class DataParallelTrainer:
         None / absent.  None or absent: the term is neither evaluated nor logged.  A number, 0.0 included, is evaluated, logged in
         `last_terms` and enters the sum with its weight, as in the reference.  lambda_depth must be 0 / None / absent: the reference's
         depth loss is commented out (utils/losses.py:294-297).
-        perceptual: any callable (x, y) -> tensor on [n, 3, 256, 256] images in (-1, 1); `lpips.LPIPS(net="vgg")`, frozen and on the
-        model's device, goes here.  It sees `losses.lpips_input(rendered)` and `losses.lpips_input(target)` (the HIP resize), loss_lpips
-        is its `.mean()` (utils/losses.py:304-309) and its gradient reaches the renders through autograd.  The network itself is not
-        part of this library."""
+        perceptual: any callable (x, y) -> tensor on [n, 3, 256, 256] images in (-1, 1), on the model's device:
+        `dgs_amd.lpips.LPIPS(net="vgg", weights=..., differentiable=True)` (HIP forward and input gradient in one call, memory bounded
+        by its chunk) or the `lpips` package's frozen module.  It sees `losses.lpips_input(rendered)` and `losses.lpips_input(target)`
+        (the HIP resize), loss_lpips is its `.mean()` (utils/losses.py:304-309) and its gradient reaches the renders through autograd.
+        The library ships no weights."""
         loss = dict(loss)
         if loss.get("lambda_depth") not in (None, 0, 0.0):
             raise ValueError("lambda_depth: the reference's depth loss is commented out (utils/losses.py:294-297); there is no such term")
