@@ -35,7 +35,8 @@
  * Invariance.  Renaming the vertices (faces and `fixed` renumbered to match) permutes the output rows and changes no byte.  Permuting
  * the faces changes nothing.  Rotating or reversing the corners of a face changes nothing.
  *
- * What this is not: no border handling, no cotangent weights, no remeshing, no repair of non-manifold edges or vertices.
+ * What this is not: no border handling, no cotangent weights, no remeshing, no repair of non-manifold edges or vertices: that is
+ * dgs_mesh_repair.h (dgs_mesh_repair_count / _emit), which extract_mesh(repair=True) runs in front of this.
  *
  * One call (the output always has V rows): device pointers, no allocation, no host synchronisation.  Built once per call: c_v by
  * integer atomic adds per vertex, an exclusive scan of the segment lengths (2 c_v for a moving vertex; the vertices that do not move

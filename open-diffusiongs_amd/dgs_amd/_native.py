@@ -618,6 +618,32 @@ def _declare_mesh_smooth(L):
     return L
 
 
+class DgsMeshRepairArgs(ctypes.Structure):
+    _fields_ = [("V", ctypes.c_int64), ("F", ctypes.c_int64), ("vertices", ctypes.c_void_p), ("faces", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p), ("topology", ctypes.c_void_p), ("out_vertices", ctypes.c_void_p), ("out_faces", ctypes.c_void_p),
+                ("max_vertices", ctypes.c_int64), ("max_faces", ctypes.c_int64), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_int64)]
+
+
+# every symbol include/dgs_mesh_repair.h declares (checked by tests/test_mesh_repair.py)
+MESH_REPAIR_SYMBOLS = ["dgs_mesh_repair_count", "dgs_mesh_repair_emit", "dgs_mesh_repair_workspace_bytes", "dgs_mesh_topology"]
+MESH_REPAIR_COUNTS = ("vertices", "faces", "invalid_faces", "null_faces", "duplicate_faces", "non_manifold_edges", "faces_removed",
+                      "non_manifold_vertices", "vertices_added", "unreferenced_vertices")        # the order of the header's `6 counts`
+MESH_TOPOLOGY_COUNTS = ("border_edges", "manifold_edges", "non_manifold_edges", "non_manifold_vertices", "referenced_vertices", "faces",
+                        "euler_characteristic")                                                 # the order of the header's `7 census`
+
+
+def _declare_mesh_repair(L):
+    if not all(hasattr(L, name) for name in MESH_REPAIR_SYMBOLS):        # a build that predates the repair (an A/B side): consumers.py refuses it there
+        return L
+    for name in ("dgs_mesh_repair_count", "dgs_mesh_repair_emit", "dgs_mesh_topology"):
+        getattr(L, name).restype = ctypes.c_int
+        getattr(L, name).argtypes = [ctypes.POINTER(DgsMeshRepairArgs), ctypes.c_void_p]
+    L.dgs_mesh_repair_workspace_bytes.restype = ctypes.c_int64
+    L.dgs_mesh_repair_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    return L
+
+
 class DgsConv3x3Args(ctypes.Structure):
     _fields_ = [("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32),
                 ("x", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("relu", ctypes.c_int32), ("y", ctypes.c_void_p)]
@@ -709,5 +735,5 @@ def _declare_lpips(L):
 _declare_raster = _declare
 
 
-def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up + decimation + attributes + smoothing + LPIPS prototypes on one library)
-    return _declare_lpips(_declare_mesh_smooth(_declare_mesh_attr(_declare_mesh_decimate(_declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L)))))))))))))
+def _declare(L):  # noqa: F811  (raster + DiT + sampler + loss + optimizer + field + EMA + mesh + mesh clean-up + decimation + attributes + smoothing + repair + LPIPS prototypes on one library)
+    return _declare_lpips(_declare_mesh_repair(_declare_mesh_smooth(_declare_mesh_attr(_declare_mesh_decimate(_declare_mesh_clean(_declare_mesh(_declare_ema(_declare_field(_declare_optim(_declare_loss(_declare_sampler(_declare_dit(_declare_raster(L))))))))))))))

@@ -23,7 +23,7 @@ STRICT_FP = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]
 # masked scores use -inf, so infinities stay honoured.
 # raster_backward.hip: the SLP vectorizer pairs loads of neighbouring struct fields of the staged entry and leaves it in scratch memory
 # (blend_backward_pair_kernel: 3 dwords stored and reloaded per step); the two-pixel arithmetic is written on explicit float pairs
-FLAGS = {"raster_forward.hip": STRICT_FP, "raster_backward.hip": STRICT_FP + ["-fno-slp-vectorize"], "sampler.hip": STRICT_FP, "loss.hip": STRICT_FP, "ssim.hip": STRICT_FP, "field.hip": STRICT_FP, "mesh.hip": STRICT_FP, "mesh_clean.hip": STRICT_FP, "mesh_decimate.hip": STRICT_FP, "mesh_attr.hip": STRICT_FP, "mesh_smooth.hip": STRICT_FP, "lpips.hip": STRICT_FP, "dit_attention.hip": ["-fno-honor-nans", "-fno-slp-vectorize"], "dit_attention_backward.hip": ["-fno-slp-vectorize"]}
+FLAGS = {"raster_forward.hip": STRICT_FP, "raster_backward.hip": STRICT_FP + ["-fno-slp-vectorize"], "sampler.hip": STRICT_FP, "loss.hip": STRICT_FP, "ssim.hip": STRICT_FP, "field.hip": STRICT_FP, "mesh.hip": STRICT_FP, "mesh_clean.hip": STRICT_FP, "mesh_decimate.hip": STRICT_FP, "mesh_attr.hip": STRICT_FP, "mesh_smooth.hip": STRICT_FP, "mesh_repair.hip": STRICT_FP, "lpips.hip": STRICT_FP, "dit_attention.hip": ["-fno-honor-nans", "-fno-slp-vectorize"], "dit_attention_backward.hip": ["-fno-slp-vectorize"]}
 
 
 def sources():

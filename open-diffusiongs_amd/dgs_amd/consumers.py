@@ -18,6 +18,9 @@ and of diffusionGS/utils/mesh_utils.py clean_mesh :119-125  (the two pymeshlab f
                                                              cluster_vertices / decimate_mesh, csrc/mesh_decimate.hip)
                                    clean_mesh :133, decimate_mesh :71  (ms.apply_coord_taubin_smoothing(), the commented alternative
                                                              of their remeshing; here smooth_mesh, csrc/mesh_smooth.hip)
+                                   clean_mesh :116-117, :127-130  (pymeshlab's duplicate-face, null-face, non-manifold edge and
+                                                             non-manifold vertex filters; here their order-free form, repair_mesh and
+                                                             the census mesh_topology, csrc/mesh_repair.hip)
 The reference writes / reads the file through the `plyfile` package (binary_little_endian 1.0, one "vertex" element, scalar
 properties in dtype order); that byte layout is restated here with numpy structured arrays -- no extra dependency.
 """
@@ -461,7 +464,7 @@ def smooth_mesh(vertices, faces, iterations=10, lam=0.5, mu=-0.53, fixed=None, r
     index outside [0, V)) and null faces (two equal indices) are ignored; a vertex no such face names, or one that more than 16,384
     name, keeps its bytes.  With return_counts also [invalid faces, null faces, vertices over that cap, unreferenced vertices], the
     call's only host synchronisation.  The same input gives the same bytes.  Not part of this: border handling (an open mesh shrinks
-    at its border), cotangent weights, remeshing, non-manifold repair.  One C call on the current stream."""
+    at its border), cotangent weights, remeshing, non-manifold repair (repair_mesh, before this).  One C call on the current stream."""
     from . import _native
     if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
         raise ValueError(f"smooth_mesh: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
@@ -509,6 +512,96 @@ def smooth_mesh(vertices, faces, iterations=10, lam=0.5, mu=-0.53, fixed=None, r
         if return_counts:
             return out, [c & 0xFFFFFFFF for c in counts.tolist()]           # the one host synchronisation
     return out
+
+
+class _Repair:
+    """The checked mesh, the library, a workspace and the argument block of dgs_mesh_repair_count / _emit / dgs_mesh_topology."""
+
+    def __init__(self, vertices, faces, lib, who):
+        from . import _native
+        if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+            raise ValueError(f"{who}: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+            raise ValueError(f"{who}: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+        if faces.device != vertices.device:
+            raise ValueError(f"{who}: vertices on {vertices.device}, faces on {faces.device}")
+        self._native = _native
+        self.L = L = lib or _native.lib()
+        if not all(hasattr(L, name) for name in _native.MESH_REPAIR_SYMBOLS):
+            raise RuntimeError(f"{who}: this build of the library predates the mesh repair -- rebuild it (`python -m dgs_amd.build`)")
+        self.vertices, self.faces = vertices.detach().contiguous(), faces.detach().contiguous()
+        self.dev = vertices.device
+        self.a = a = _native.DgsMeshRepairArgs()
+        a.V, a.F = self.vertices.shape[0], self.faces.shape[0]
+        a.workspace_bytes = L.dgs_mesh_repair_workspace_bytes(a.V, a.F)
+        if a.workspace_bytes <= 0:
+            raise ValueError(f"{who}: unsupported size V = {a.V}, F = {a.F} (at most 2^30 and 2^28)")
+        self.ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=self.dev)
+        a.workspace = ctypes.c_void_p(self.ws.data_ptr())
+        a.vertices = ctypes.c_void_p(self.vertices.data_ptr()) if a.V else None
+        a.faces = ctypes.c_void_p(self.faces.data_ptr()) if a.F else None
+        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream) if vertices.is_cuda else None
+
+    def call(self, name):
+        rc = getattr(self.L, name)(ctypes.byref(self.a), self.stream)
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed: {rc} ({self._native.status_string(self.L, rc)})")
+
+    def done(self, *more):
+        if self.vertices.is_cuda:
+            for t in (self.vertices, self.faces, self.ws) + more:
+                t.record_stream(torch.cuda.current_stream(self.dev))
+
+
+def repair_mesh(vertices, faces, return_counts=False, lib=None):
+    """The four repair filters of the reference's clean_mesh (repair=True) on the mesh's device (include/dgs_mesh_repair.h,
+    csrc/mesh_repair.hip; MeshLab's meshing_remove_null_faces, meshing_remove_duplicate_faces, meshing_repair_non_manifold_edges with
+    method 0 and meshing_repair_non_manifold_vertices with vertdispratio 0, in their order-free form): faces with an index outside
+    [0, V), with two equal indices or without area go; of the faces on the same three vertices the one of the smallest index stays; on
+    an edge of three or more faces the two largest stay (ties: the smaller index) and the others go; a vertex whose faces form several
+    fans keeps the fan of its first corner and gets one copy, the same 12 bytes, for each other fan; vertices no face names go.
+    vertices float32 [V, 3], faces int32 [F, 3] -> (vertices', faces') on the same device: the kept vertices in input order, then the
+    copies; the kept faces in input order, with their orientation.  A manifold mesh without such faces and vertices comes back byte for
+    byte.  With return_counts also a dict of the ten counts (_native.MESH_REPAIR_COUNTS: vertices, faces, invalid_faces, null_faces,
+    duplicate_faces, non_manifold_edges, faces_removed, non_manifold_vertices, vertices_added, unreferenced_vertices).  The same input
+    gives the same bytes.  Orientation is neither checked nor repaired; an edge that kept a face which another edge removed becomes a
+    border.  dgs_mesh_repair_count, ONE readback of the ten counts to size the outputs, dgs_mesh_repair_emit."""
+    with torch.no_grad():
+        r = _Repair(vertices, faces, lib, "repair_mesh")
+        counts_dev = torch.empty(len(r._native.MESH_REPAIR_COUNTS), dtype=torch.int32, device=r.dev)   # the call writes uint32 [10]
+        r.a.counts = ctypes.c_void_p(counts_dev.data_ptr())
+        r.call("dgs_mesh_repair_count")
+        counts = [c & 0xFFFFFFFF for c in counts_dev.tolist()]              # the feature's one host synchronisation
+        if counts[0] == 0xFFFFFFFF:
+            raise RuntimeError("repair_mesh: dgs_mesh_repair_count found no slot for a face or an edge in its tables")
+        nv, nf = counts[:2]
+        out_v = torch.empty((nv, 3), dtype=torch.float32, device=r.dev)
+        out_f = torch.empty((nf, 3), dtype=torch.int32, device=r.dev)
+        if nf:
+            r.a.out_vertices, r.a.out_faces = ctypes.c_void_p(out_v.data_ptr()), ctypes.c_void_p(out_f.data_ptr())
+            r.a.max_vertices, r.a.max_faces = nv, nf
+            r.call("dgs_mesh_repair_emit")
+        r.done(counts_dev)
+    return (out_v, out_f, dict(zip(r._native.MESH_REPAIR_COUNTS, counts))) if return_counts else (out_v, out_f)
+
+
+def mesh_topology(vertices, faces, lib=None):
+    """The census of include/dgs_mesh_repair.h (dgs_mesh_topology) on the mesh's device -> a dict of integers
+    (_native.MESH_TOPOLOGY_COUNTS): border_edges (one face), manifold_edges (two), non_manifold_edges (three or more),
+    non_manifold_vertices (the faces around the vertex, joined through its edges of exactly two faces, form more than one fan),
+    referenced_vertices, faces, euler_characteristic (referenced vertices - edges + faces), over the faces whose three indices lie in
+    [0, V) and differ; a face that occurs twice counts twice, and the coordinates are not read.  It decides nothing for repair_mesh:
+    it is the check of a raw mesh (is a repair needed?) as well as of a repaired one.  One C call and one readback of seven integers."""
+    with torch.no_grad():
+        r = _Repair(vertices, faces, lib, "mesh_topology")
+        out = torch.empty(len(r._native.MESH_TOPOLOGY_COUNTS), dtype=torch.int64, device=r.dev)
+        r.a.topology = ctypes.c_void_p(out.data_ptr())
+        r.call("dgs_mesh_topology")
+        numbers = out.tolist()                                              # the host synchronisation
+        r.done(out)
+        if numbers[0] < 0:
+            raise RuntimeError("mesh_topology: dgs_mesh_topology found no slot for an edge in its table")
+    return dict(zip(r._native.MESH_TOPOLOGY_COUNTS, numbers))
 
 
 def mesh_attributes(pc, points, num_blocks=64, reach=2, attr=None, want=("colors", "normals", "density"), lib=None):
@@ -584,14 +677,17 @@ def mesh_attributes(pc, points, num_blocks=64, reach=2, attr=None, want=("colors
 
 
 def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0, decimate_target=0, attributes=False,
-                 smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53):
+                 smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, repair=False):
     """gs_core.py:855-869: extract_fields (sets pc.mesh_center / pc.mesh_scale), marching cubes at density_thresh,
     vertices / (resolution - 1) * 2 - 1 -> Mesh on pc's device.  min_f / min_d > 0 then drop the floaters as the first two
     filters of the reference's clean_mesh do (remove_small_components on the mesh in [-1, 1]^3, which is what clean_mesh sees; the
     reference's values are min_f=64, min_d=20); with both 0, the default, that path is not entered.  decimate_target > 0 then brings
     a mesh of more faces down to at most that many by vertex clustering on the device (decimate_mesh; the reference's value is 1e5,
     by pymeshlab's quadric edge collapse); 0, the default, does not enter that path, and with all three 0 the raw level set is
-    returned.  The rest of clean_mesh (merging close vertices, non-manifold repair, remeshing: pymeshlab) is not part of this: hand it
+    returned.  repair=True then runs the repair filters of clean_mesh on that mesh (repair_mesh: null and duplicate faces,
+    non-manifold edges and vertices, unreferenced vertices; the reference's clean_mesh has repair=True as its default), so that the
+    smoothing and the attributes see the repaired mesh; False, the default, does not enter that path.  The rest of clean_mesh
+    (merging close vertices, remeshing: pymeshlab) is not part of this: hand it
     mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy().  smooth_iterations > 0 then smooths the vertices of that
     mesh with that many Taubin iterations of weights smooth_lambda, smooth_mu (smooth_mesh: the commented alternative of the reference's
     remeshing; the faces stay); 0, the default, does not enter that path.  attributes=True then evaluates mesh_attributes at the
@@ -604,6 +700,8 @@ def extract_mesh(pc, density_thresh=0.005, resolution=256, num_blocks=64, lib=No
         vertices, triangles = remove_small_components(vertices, triangles, min_f=min_f, min_d=min_d, lib=lib)
     if decimate_target:
         vertices, triangles = decimate_mesh(vertices, triangles, decimate_target, lib=lib)
+    if repair:
+        vertices, triangles = repair_mesh(vertices, triangles, lib=lib)
     if smooth_iterations:
         vertices = smooth_mesh(vertices, triangles, smooth_iterations, smooth_lambda, smooth_mu, lib=lib)
     if attributes:

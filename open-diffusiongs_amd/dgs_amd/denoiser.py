@@ -150,7 +150,7 @@ class GaussianModel:
         return consumers.extract_fields(self, resolution, num_blocks, relax_ratio, lib)
 
     def extract_mesh(self, density_thresh=0.005, resolution=256, num_blocks=64, lib=None, min_f=0, min_d=0, decimate_target=0, attributes=False,
-                     smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53):
+                     smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, repair=False):
         """gs_core.py:855-869 -> consumers.Mesh(vertices [V, 3] in [-1, 1]^3, faces [F, 3]) on the model's device: extract_fields,
         then marching cubes on the device (csrc/mesh.hip); sets self.mesh_center / self.mesh_scale as extract_fields does.
         min_f / min_d > 0 drop the small components on the device as well (csrc/mesh_clean.hip; the reference's clean_mesh uses
@@ -158,10 +158,14 @@ class GaussianModel:
         device (consumers.decimate_mesh, csrc/mesh_decimate.hip; the reference's value is 1e5, by quadric edge collapse).  The
         default 0, 0, 0 returns the raw level set.  smooth_iterations > 0 then smooths the vertices with that many Taubin iterations
         of weights smooth_lambda, smooth_mu (consumers.smooth_mesh, csrc/mesh_smooth.hip); 0, the default, does not enter that path.
-        attributes=True also fills the mesh's colors / normals / density at the final vertices (mesh_attributes)."""
+        attributes=True also fills the mesh's colors / normals / density at the final vertices (mesh_attributes).  repair=True runs
+        the repair filters of the reference's clean_mesh on the device behind the decimation and in front of the smoothing and the
+        attributes (consumers.repair_mesh, csrc/mesh_repair.hip: null and duplicate faces, non-manifold edges and vertices); False,
+        the default, does not enter that path."""
         from . import consumers
         return consumers.extract_mesh(self, density_thresh, resolution, num_blocks, lib, min_f=min_f, min_d=min_d, decimate_target=decimate_target,
-                                      attributes=attributes, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
+                                      attributes=attributes, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
+                                      repair=repair)
 
     def mesh_attributes(self, points, num_blocks=64, reach=2, attr=None, want=("colors", "normals", "density"), lib=None):
         """Colour, outward normal and density of the Gaussians at `points` [V, 3] of the normalised cube (the vertices of extract_mesh)
