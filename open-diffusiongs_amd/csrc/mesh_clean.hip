@@ -7,14 +7,11 @@
 //   clean_link_kernel     thread = face: validity (invalid faces counted), ref[a] = ref[b] = ref[c] = 1, and atomicMin of each vertex's link
 //                         to the face's smallest index: a forest inside the components.  It loses edges; the hook launch takes all again.
 //   clean_compress_kernel thread = vertex, its own launch (nothing writes link[], plain loads): parent[v] = the root of v's link tree.
-//   clean_hook_kernel     thread = face: union(a, b), union(a, c) in a lock-free union-find over the vertex indices, started from the three
-//                         parents and skipped when those are equal already, which after the two launches before holds for nearly every
-//                         face (hooking from parent[v] = v took 1.35 ms at 2.09 M faces, this form 0.07 + 0.04 + 0.58 ms).  A root is
-//                         hooked under a SMALLER root with one atomicCAS on its own parent word, and path halving only ever lowers a
-//                         parent (atomicMin to a grandparent), so parent[x] <= x always holds, no cycle can form and the root of a tree
-//                         is the smallest index of its set.  Nothing waits: a CAS that loses starts over from the new roots.  The XCDs'
-//                         L2s are not coherent for plain loads inside a launch, so EVERY access to parent[] in this launch is an
-//                         agent-scope atomic (relaxed load, atomicMin, atomicCAS).
+//   clean_hook_kernel     thread = face: union(a, b), union(a, c) in the lock-free union-find of csrc/mesh_common.h over the vertex indices
+//                         (the root of a tree is the smallest index of its set; every access to parent[] in this launch is an agent-scope
+//                         atomic), started from the three parents and skipped when those are equal already, which after the two launches
+//                         before holds for nearly every face (hooking from parent[v] = v took 1.35 ms at 2.09 M faces, this form
+//                         0.07 + 0.04 + 0.58 ms).
 //   clean_flatten_kernel  thread = vertex, the next launch (plain loads now see the final links): lab[v] = root of v = canonical label.
 //   clean_faces_kernel    lane = face: cnt[lab] += 1.  The lanes of a wave that share the leading lane's label add their number together
 //                         (two rounds, whatever is left goes alone), the sums go to a 256-slot table of the workgroup in LDS, and the
@@ -47,6 +44,7 @@
 
 #include "dgs_device.h"
 #include "dgs_mesh_clean.h"
+#include "mesh_common.h"
 
 namespace dgs {
 
@@ -66,73 +64,24 @@ struct CleanWs {
     uint32_t* misc;                                  // [CLEAN_MISC_WORDS] the mesh's box, components, components kept, invalid faces
     int64_t vblocks, fblocks, bytes;
     __host__ CleanWs(void* base, int64_t V, int64_t F) {
-        uintptr_t at = reinterpret_cast<uintptr_t>(base);                // base == nullptr: only `bytes` is used
-        auto take = [&at](int64_t n) { const uintptr_t p = at; at += (uintptr_t)((4 * n + 15) & ~(int64_t)15); return reinterpret_cast<uint32_t*>(p); };
+        MeshCarver c(base);                                              // base == nullptr: only `bytes` is used
         vblocks = (V + CLEAN_WG - 1) / CLEAN_WG;
         fblocks = (F + CLEAN_WG - 1) / CLEAN_WG;
-        misc = take(CLEAN_MISC_WORDS);
-        link = take(V);
-        parent = take(V);
-        lab = take(V);
-        ref = take(V);
-        cnt = take(V);
-        keep = take(V);
-        box = take(6 * V);
-        voff = take(V);
-        foff = take(F);
-        vblk = take(vblocks);
-        fblk = take(fblocks);
-        bytes = (int64_t)(at - reinterpret_cast<uintptr_t>(base));
+        misc = c.take<uint32_t>(CLEAN_MISC_WORDS);
+        link = c.take<uint32_t>(V);
+        parent = c.take<uint32_t>(V);
+        lab = c.take<uint32_t>(V);
+        ref = c.take<uint32_t>(V);
+        cnt = c.take<uint32_t>(V);
+        keep = c.take<uint32_t>(V);
+        box = c.take<uint32_t>(6 * V);
+        voff = c.take<uint32_t>(V);
+        foff = c.take<uint32_t>(F);
+        vblk = c.take<uint32_t>(vblocks);
+        fblk = c.take<uint32_t>(fblocks);
+        bytes = c.used();
     }
 };
-
-// Order-preserving image of a float: a < b as floats <=> key(a) < key(b) as unsigned (-0 below +0; a NaN is just some key).
-__device__ __forceinline__ uint32_t clean_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : u | 0x80000000u;
-}
-__device__ __forceinline__ float clean_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? k & 0x7fffffffu : ~k); }
-
-__device__ __forceinline__ bool clean_valid(int a, int b, int c, uint32_t V) { return (uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V; }
-
-// A relaxed agent-scope atomic load: the value in memory, not a line this XCD's L2 may still hold from before another XCD's atomic.
-__device__ __forceinline__ uint32_t clean_load(uint32_t* p) {
-#ifdef HIPEMU
-    return *p;
-#else
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
-
-// atomicMax that first looks: the words only grow, so a value that does not exceed what is there already needs no atomic.  Nearly
-// every wave inside a large component is in that position, and the atomics of one address are served one after another.
-__device__ __forceinline__ void clean_raise(uint32_t* p, uint32_t v) {
-    if (v > clean_load(p)) atomicMax(p, v);
-}
-
-// ---- union-find; every access to parent[] is an agent-scope atomic ----
-// Root of x, halving the path: parent[x] is lowered to x's grandparent, an ancestor with a smaller index.
-__device__ __forceinline__ uint32_t clean_find(uint32_t* parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = clean_load(parent + x);
-        if (p == x) return x;
-        const uint32_t g = clean_load(parent + p);
-        if (g == p) return p;
-        atomicMin(parent + x, g);
-        x = g;
-    }
-}
-
-// -> the root of the united set at the time of the call.
-__device__ __forceinline__ uint32_t clean_union(uint32_t* parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = clean_find(parent, a);
-        b = clean_find(parent, b);
-        if (a == b) return a;
-        const uint32_t big = a > b ? a : b, small = a > b ? b : a;
-        if (atomicCAS(parent + big, big, small) == big) return small;   // `big` was still a root: hooked.  Otherwise someone hooked it first: again
-    }
-}
 
 // The lanes among `pending` that hold the label of the first pending lane, as a mask; *leader is that lane.  Wave-uniform control flow.
 __device__ __forceinline__ uint64_t clean_same_label(bool pending, uint32_t label, int lane, int* leader, uint32_t* leader_label) {
@@ -140,15 +89,6 @@ __device__ __forceinline__ uint64_t clean_same_label(bool pending, uint32_t labe
     *leader = pm ? __ffsll((long long)pm) - 1 : 0;
     *leader_label = __shfl(label, *leader);
     return wave_ballot(pending && label == *leader_label);
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 1; d < DGS_WAVE; d <<= 1) {
-        const uint32_t o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(CLEAN_WG) void clean_init_kernel(uint32_t V, CleanWs ws) {
@@ -170,7 +110,7 @@ __global__ __launch_bounds__(CLEAN_WG) void clean_link_kernel(DgsMeshCleanArgs a
     if (f < (uint32_t)a.F) {
         const int32_t* t = a.faces + 3 * (size_t)f;
         const int i = t[0], j = t[1], k = t[2];
-        if (clean_valid(i, j, k, V)) {
+        if (mesh_face_valid(i, j, k, V)) {
             ws.ref[i] = 1;                                                // the same value from every writer
             ws.ref[j] = 1;
             ws.ref[k] = 1;
@@ -200,13 +140,13 @@ __global__ __launch_bounds__(CLEAN_WG) void clean_hook_kernel(DgsMeshCleanArgs a
     if (f >= (uint32_t)a.F) return;
     const int32_t* t = a.faces + 3 * (size_t)f;
     const int i = t[0], j = t[1], k = t[2];
-    if (!clean_valid(i, j, k, V)) return;
+    if (!mesh_face_valid(i, j, k, V)) return;
     // Start from the parents (members of the same sets).  Three equal parents: one set already, and no walk to the root, whose word
     // every walk of a large component ends on.
-    const uint32_t pi = clean_load(ws.parent + i), pj = clean_load(ws.parent + j), pk = clean_load(ws.parent + k);
+    const uint32_t pi = mesh_load(ws.parent + i), pj = mesh_load(ws.parent + j), pk = mesh_load(ws.parent + k);
     if (pi != pj || pi != pk) {
-        const uint32_t r = pi != pj ? clean_union(ws.parent, pi, pj) : pi;
-        if (pk != r) clean_union(ws.parent, r, pk);
+        const uint32_t r = pi != pj ? mesh_union(ws.parent, pi, pj) : pi;
+        if (pk != r) mesh_union(ws.parent, r, pk);
     }
 }
 
@@ -251,7 +191,7 @@ __global__ __launch_bounds__(CLEAN_WG) void clean_faces_kernel(DgsMeshCleanArgs 
         if (f < F) {
             const int32_t* t = a.faces + 3 * (size_t)f;
             const int i = t[0];
-            if (clean_valid(i, t[1], t[2], V)) {
+            if (mesh_face_valid(i, t[1], t[2], V)) {
                 pending = true;
                 label = ws.lab[i];
             }
@@ -282,14 +222,14 @@ __global__ __launch_bounds__(CLEAN_WG) void clean_box_kernel(DgsMeshCleanArgs a,
         const float* p = a.vertices + 3 * (size_t)v;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const uint32_t k = clean_key(p[c]);
+            const uint32_t k = mesh_float_key(p[c]);
             key[c] = ~k;
             key[3 + c] = k;
         }
     }
 #pragma unroll
     for (int c = 0; c < 6; ++c) {                                         // the mesh's box: wave, workgroup, six atomics a workgroup
-        const uint32_t m = wave_max(key[c]);
+        const uint32_t m = mesh_wave_max(key[c]);
         if (lane == 0) part[wave][c] = m;
     }
 #pragma unroll
@@ -301,22 +241,22 @@ __global__ __launch_bounds__(CLEAN_WG) void clean_box_kernel(DgsMeshCleanArgs a,
         if (same != 0) {                                                  // wave-uniform
 #pragma unroll
             for (int c = 0; c < 6; ++c) {
-                const uint32_t m = wave_max(mine ? key[c] : 0u);
-                if (lane == leader) clean_raise(ws.box + 6 * (size_t)leader_label + c, m);
+                const uint32_t m = mesh_wave_max(mine ? key[c] : 0u);
+                if (lane == leader) mesh_raise(ws.box + 6 * (size_t)leader_label + c, m);
             }
         }
         pending = pending && !mine;
     }
     if (pending) {
 #pragma unroll
-        for (int c = 0; c < 6; ++c) clean_raise(ws.box + 6 * (size_t)label + c, key[c]);
+        for (int c = 0; c < 6; ++c) mesh_raise(ws.box + 6 * (size_t)label + c, key[c]);
     }
     __syncthreads();
     if (threadIdx.x < 6) {
         uint32_t m = 0;
 #pragma unroll
         for (int w = 0; w < CLEAN_WG / DGS_WAVE; ++w) m = part[w][threadIdx.x] > m ? part[w][threadIdx.x] : m;
-        if (m != 0) clean_raise(ws.misc + CLEAN_BOX + threadIdx.x, m);
+        if (m != 0) mesh_raise(ws.misc + CLEAN_BOX + threadIdx.x, m);
     }
 }
 
@@ -324,7 +264,7 @@ __global__ __launch_bounds__(CLEAN_WG) void clean_box_kernel(DgsMeshCleanArgs a,
 __device__ __forceinline__ double clean_diag2(const uint32_t* box) {
     double d[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) d[c] = (double)clean_unkey(box[3 + c]) - (double)clean_unkey(~box[c]);
+    for (int c = 0; c < 3; ++c) d[c] = (double)mesh_float_unkey(box[3 + c]) - (double)mesh_float_unkey(~box[c]);
     return d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
 }
 
@@ -334,7 +274,7 @@ __device__ __forceinline__ double clean_diag2(const uint32_t* box) {
 __global__ __launch_bounds__(DGS_WAVE) void clean_threshold_kernel(CleanWs ws, double pp) {
     __shared__ double square[3];
     if (threadIdx.x < 3) {
-        const double d = (double)clean_unkey(ws.misc[CLEAN_BOX + 3 + threadIdx.x]) - (double)clean_unkey(~ws.misc[CLEAN_BOX + threadIdx.x]);
+        const double d = (double)mesh_float_unkey(ws.misc[CLEAN_BOX + 3 + threadIdx.x]) - (double)mesh_float_unkey(~ws.misc[CLEAN_BOX + threadIdx.x]);
         square[threadIdx.x] = d * d;
     }
     __syncthreads();
@@ -367,7 +307,7 @@ __device__ __forceinline__ bool clean_face_kept(const DgsMeshCleanArgs& a, const
     t[0] = p[0];
     t[1] = p[1];
     t[2] = p[2];
-    return clean_valid(t[0], t[1], t[2], (uint32_t)a.V) && ws.keep[ws.lab[t[0]]] != 0;
+    return mesh_face_valid(t[0], t[1], t[2], (uint32_t)a.V) && ws.keep[ws.lab[t[0]]] != 0;
 }
 
 __global__ __launch_bounds__(CLEAN_WG) void clean_vscan_kernel(DgsMeshCleanArgs a, CleanWs ws) {
@@ -391,25 +331,10 @@ __global__ __launch_bounds__(CLEAN_WG) void clean_fscan_kernel(DgsMeshCleanArgs 
     if (threadIdx.x == 0) ws.fblk[blockIdx.x] = total;
 }
 
-// Exclusive scan of n block totals in place by one workgroup of 1,024: a contiguous piece per thread, a scan of the pieces' sums.
-__device__ __forceinline__ uint32_t clean_scan_blocks(uint32_t* blk, int64_t n, uint32_t* scratch) {
-    const int64_t per = (n + 1023) / 1024, c0 = per * threadIdx.x, c1 = c0 + per < n ? c0 + per : n;
-    uint32_t s = 0;
-    for (int64_t c = c0; c < c1; ++c) s += blk[c];
-    uint32_t total;
-    uint32_t run = block_exclusive_scan<1024>(s, scratch, &total);
-    for (int64_t c = c0; c < c1; ++c) {
-        const uint32_t here = blk[c];
-        blk[c] = run;
-        run += here;
-    }
-    return total;
-}
-
 __global__ __launch_bounds__(1024) void clean_sums_kernel(DgsMeshCleanArgs a, CleanWs ws) {
     __shared__ uint32_t scratch[1024 / DGS_WAVE + 1];
-    const uint32_t nv = clean_scan_blocks(ws.vblk, ws.vblocks, scratch);
-    const uint32_t nf = clean_scan_blocks(ws.fblk, ws.fblocks, scratch);
+    const uint32_t nv = mesh_scan_blocks(ws.vblk, ws.vblocks, scratch);
+    const uint32_t nf = mesh_scan_blocks(ws.fblk, ws.fblocks, scratch);
     if (threadIdx.x == 0) {
         a.counts[0] = nv;
         a.counts[1] = nf;
@@ -429,11 +354,7 @@ __global__ __launch_bounds__(CLEAN_WG) void clean_emit_vertices_kernel(DgsMeshCl
     if (v >= (uint32_t)a.V || !clean_vertex_kept(ws, v)) return;
     const uint32_t at = ws.vblk[blockIdx.x] + ws.voff[v];
     if ((int64_t)at >= a.max_vertices) return;
-    const uint32_t* in = reinterpret_cast<const uint32_t*>(a.vertices) + 3 * (size_t)v;   // the 12 bytes, not three floats: NaN payloads stay
-    uint32_t* out = reinterpret_cast<uint32_t*>(a.out_vertices) + 3 * (size_t)at;
-    out[0] = in[0];
-    out[1] = in[1];
-    out[2] = in[2];
+    mesh_copy_vertex_bytes(a.vertices, v, a.out_vertices, at);
 }
 
 __global__ __launch_bounds__(CLEAN_WG) void clean_emit_faces_kernel(DgsMeshCleanArgs a, CleanWs ws) {
@@ -441,7 +362,7 @@ __global__ __launch_bounds__(CLEAN_WG) void clean_emit_faces_kernel(DgsMeshClean
     if (f >= (uint32_t)a.F) return;
     int t[3];
     const bool kept = clean_face_kept(a, ws, f, t);
-    if (a.labels) a.labels[f] = clean_valid(t[0], t[1], t[2], (uint32_t)a.V) ? (int32_t)ws.lab[t[0]] : -1;
+    if (a.labels) a.labels[f] = mesh_face_valid(t[0], t[1], t[2], (uint32_t)a.V) ? (int32_t)ws.lab[t[0]] : -1;
     if (!kept) return;
     const uint32_t at = ws.fblk[blockIdx.x] + ws.foff[f];
     if ((int64_t)at >= a.max_faces) return;

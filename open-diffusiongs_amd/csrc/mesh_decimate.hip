@@ -52,6 +52,7 @@
 
 #include "dgs_device.h"
 #include "dgs_mesh_decimate.h"
+#include "mesh_common.h"
 
 namespace dgs {
 
@@ -80,8 +81,7 @@ struct DecWs {
     unsigned long long* sum;                         // [K, 3] by rank, emit: the sums of their offsets
     int64_t K, pieces, slots, oblocks, fblocks, kblocks, vblocks, zero_bytes, acc_bytes, bytes;
     __host__ DecWs(void* base, int64_t V, int64_t F, int64_t n) {
-        uintptr_t at = reinterpret_cast<uintptr_t>(base);                // base == nullptr: only the sizes are used
-        auto take = [&at](int64_t words) { const uintptr_t p = at; at += (uintptr_t)((4 * words + 15) & ~(int64_t)15); return reinterpret_cast<uint32_t*>(p); };
+        MeshCarver c(base);                                              // base == nullptr: only the sizes are used
         const int64_t cells = n * n * n;
         K = V < cells ? V : cells;
         pieces = (cells + 64 * DEC_PIECE - 1) / (64 * DEC_PIECE);
@@ -91,67 +91,29 @@ struct DecWs {
         fblocks = (F + DEC_WG - 1) / DEC_WG;
         kblocks = (K + DEC_WG - 1) / DEC_WG;
         oblocks = (pieces + DEC_WG - 1) / DEC_WG;
-        misc = take(DEC_MISC_WORDS);                                     // misc, ref, used, mask: zeroed by one memset of the count call
-        ref = take(V);
-        used = take(K);
-        mask = reinterpret_cast<uint64_t*>(take(2 * DEC_PIECE * pieces));
-        zero_bytes = (int64_t)(at - reinterpret_cast<uintptr_t>(base));
-        vrank = take(V);
-        fslot = take(F);
-        foff = take(F);
-        table = take(slots);
-        spre = take(pieces);
-        oblk = take(oblocks);
-        cellof = take(K);
-        uoff = take(K);
-        fblk = take(fblocks);
-        ublk = take(kblocks);
-        lblk = take(fblocks);
-        const uintptr_t acc = at;                                        // cnt, sum: zeroed by the memset of the emit call
-        cnt = take(K);
-        sum = reinterpret_cast<unsigned long long*>(take(6 * K));
-        acc_bytes = (int64_t)(at - acc);
-        bytes = (int64_t)(at - reinterpret_cast<uintptr_t>(base));
+        misc = c.take<uint32_t>(DEC_MISC_WORDS);                         // misc, ref, used, mask: zeroed by one memset of the count call
+        ref = c.take<uint32_t>(V);
+        used = c.take<uint32_t>(K);
+        mask = c.take<uint64_t>(DEC_PIECE * pieces);
+        zero_bytes = c.used();
+        vrank = c.take<uint32_t>(V);
+        fslot = c.take<uint32_t>(F);
+        foff = c.take<uint32_t>(F);
+        table = c.take<uint32_t>(slots);
+        spre = c.take<uint32_t>(pieces);
+        oblk = c.take<uint32_t>(oblocks);
+        cellof = c.take<uint32_t>(K);
+        uoff = c.take<uint32_t>(K);
+        fblk = c.take<uint32_t>(fblocks);
+        ublk = c.take<uint32_t>(kblocks);
+        lblk = c.take<uint32_t>(fblocks);
+        const int64_t acc = c.used();                                    // cnt, sum: zeroed by the memset of the emit call
+        cnt = c.take<uint32_t>(K);
+        sum = c.take<unsigned long long>(3 * K);
+        acc_bytes = c.used() - acc;
+        bytes = c.used();
     }
 };
-
-// Order-preserving image of a float (csrc/mesh_clean.hip, clean_key): a < b as floats <=> key(a) < key(b) as unsigned.
-__device__ __forceinline__ uint32_t dec_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : u | 0x80000000u;
-}
-__device__ __forceinline__ float dec_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? k & 0x7fffffffu : ~k); }
-
-__device__ __forceinline__ bool dec_valid(int a, int b, int c, uint32_t V) { return (uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V; }
-
-// Relaxed agent-scope atomic loads: the value in memory, not a line this XCD's L2 may still hold from before another XCD's atomic.
-__device__ __forceinline__ uint32_t dec_load(uint32_t* p) {
-#ifdef HIPEMU
-    return *p;
-#else
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
-__device__ __forceinline__ unsigned long long dec_load64(unsigned long long* p) {
-#ifdef HIPEMU
-    return *p;
-#else
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
-
-__device__ __forceinline__ void dec_raise(uint32_t* p, uint32_t v) {
-    if (v > dec_load(p)) atomicMax(p, v);
-}
-
-__device__ __forceinline__ uint32_t dec_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 1; d < DGS_WAVE; d <<= 1) {
-        const uint32_t o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 __device__ __forceinline__ const double* dec_params(const DecWs& ws) { return reinterpret_cast<const double*>(ws.misc + DEC_PARAMS); }
 
@@ -181,7 +143,7 @@ __global__ __launch_bounds__(DEC_WG) void dec_ref_kernel(DgsMeshDecimateArgs a, 
     if (f < (uint32_t)a.F) {
         const int32_t* t = a.faces + 3 * (size_t)f;
         const int i = t[0], j = t[1], k = t[2];
-        if (dec_valid(i, j, k, V)) {
+        if (mesh_face_valid(i, j, k, V)) {
             ws.ref[i] = 1;                                                // the same value from every writer
             ws.ref[j] = 1;
             ws.ref[k] = 1;
@@ -202,14 +164,14 @@ __global__ __launch_bounds__(DEC_WG) void dec_box_kernel(DgsMeshDecimateArgs a, 
         const float* p = a.vertices + 3 * (size_t)v;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const uint32_t k = dec_key(p[c]);
+            const uint32_t k = mesh_float_key(p[c]);
             key[c] = ~k;
             key[3 + c] = k;
         }
     }
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
-        const uint32_t m = dec_wave_max(key[c]);
+        const uint32_t m = mesh_wave_max(key[c]);
         if (lane == 0) part[wave][c] = m;
     }
     __syncthreads();
@@ -217,7 +179,7 @@ __global__ __launch_bounds__(DEC_WG) void dec_box_kernel(DgsMeshDecimateArgs a, 
         uint32_t m = 0;
 #pragma unroll
         for (int w = 0; w < DEC_WG / DGS_WAVE; ++w) m = part[w][threadIdx.x] > m ? part[w][threadIdx.x] : m;
-        if (m != 0) dec_raise(ws.misc + DEC_BOX + threadIdx.x, m);
+        if (m != 0) mesh_raise(ws.misc + DEC_BOX + threadIdx.x, m);
     }
 }
 
@@ -226,8 +188,8 @@ __global__ __launch_bounds__(DGS_WAVE) void dec_params_kernel(DgsMeshDecimateArg
     __shared__ double extent[3];
     double* params = reinterpret_cast<double*>(ws.misc + DEC_PARAMS);
     if (threadIdx.x < 3) {
-        const double lo = (double)dec_unkey(~ws.misc[DEC_BOX + threadIdx.x]);
-        extent[threadIdx.x] = (double)dec_unkey(ws.misc[DEC_BOX + 3 + threadIdx.x]) - lo;
+        const double lo = (double)mesh_float_unkey(~ws.misc[DEC_BOX + threadIdx.x]);
+        extent[threadIdx.x] = (double)mesh_float_unkey(ws.misc[DEC_BOX + 3 + threadIdx.x]) - lo;
         params[threadIdx.x] = lo;
     }
     __syncthreads();
@@ -251,7 +213,7 @@ __global__ __launch_bounds__(DEC_WG) void dec_cell_kernel(DgsMeshDecimateArgs a,
     ws.vrank[v] = cell;
     unsigned long long* word = reinterpret_cast<unsigned long long*>(ws.mask) + (cell >> 6);
     const unsigned long long bit = 1ull << (cell & 63);
-    if (!(dec_load64(word) & bit)) atomicOr(word, bit);
+    if (!(mesh_load(word) & bit)) atomicOr(word, bit);
 }
 
 __global__ __launch_bounds__(DEC_WG) void dec_occ_kernel(DecWs ws) {
@@ -273,25 +235,10 @@ __global__ __launch_bounds__(DEC_WG) void dec_occ_kernel(DecWs ws) {
     if (threadIdx.x == 0) ws.oblk[blockIdx.x] = total;
 }
 
-// Exclusive scan of n block totals in place by one workgroup of 1,024 (the form of clean_scan_blocks) -> their sum.
-__device__ __forceinline__ uint32_t dec_scan_blocks(uint32_t* blk, int64_t n, uint32_t* scratch) {
-    const int64_t per = (n + 1023) / 1024, c0 = per * threadIdx.x, c1 = c0 + per < n ? c0 + per : n;
-    uint32_t s = 0;
-    for (int64_t c = c0; c < c1; ++c) s += blk[c];
-    uint32_t total;
-    uint32_t run = block_exclusive_scan<1024>(s, scratch, &total);
-    for (int64_t c = c0; c < c1; ++c) {
-        const uint32_t here = blk[c];
-        blk[c] = run;
-        run += here;
-    }
-    return total;
-}
-
 __global__ __launch_bounds__(1024) void dec_occ_sums_kernel(DecWs ws) {
     __shared__ uint32_t scratch[1024 / DGS_WAVE + 1];
     if (ws.misc[DEC_EMPTY]) return;
-    const uint32_t occupied = dec_scan_blocks(ws.oblk, ws.oblocks, scratch);
+    const uint32_t occupied = mesh_scan_blocks(ws.oblk, ws.oblocks, scratch);
     if (threadIdx.x == 0) ws.misc[DEC_OCCUPIED] = occupied;
 }
 
@@ -311,17 +258,6 @@ __global__ __launch_bounds__(DEC_WG) void dec_rank_kernel(DgsMeshDecimateArgs a,
     ws.cellof[r] = cell;                                                  // the same value from every writer
 }
 
-struct DecTriple {
-    uint32_t s0, s1, s2;                                                  // ascending
-};
-__device__ __forceinline__ DecTriple dec_sorted(uint32_t x, uint32_t y, uint32_t z) {
-    uint32_t t;
-    if (x > y) { t = x; x = y; y = t; }
-    if (y > z) { t = y; y = z; z = t; }
-    if (x > y) { t = x; x = y; y = t; }
-    return {x, y, z};
-}
-
 __global__ __launch_bounds__(DEC_WG) void dec_insert_kernel(DgsMeshDecimateArgs a, DecWs ws) {
     if (ws.misc[DEC_EMPTY]) return;
     const uint32_t f = blockIdx.x * DEC_WG + threadIdx.x, V = (uint32_t)a.V, slot_mask = (uint32_t)(ws.slots - 1);
@@ -329,10 +265,10 @@ __global__ __launch_bounds__(DEC_WG) void dec_insert_kernel(DgsMeshDecimateArgs 
         const int32_t* t = a.faces + 3 * (size_t)f;
         const int i = t[0], j = t[1], k = t[2];
         uint32_t mine = DEC_NONE;
-        if (dec_valid(i, j, k, V)) {
+        if (mesh_face_valid(i, j, k, V)) {
             const uint32_t ri = ws.vrank[i], rj = ws.vrank[j], rk = ws.vrank[k];
             if (ri != rj && ri != rk && rj != rk) {                           // otherwise degenerate: no slot
-                const DecTriple key = dec_sorted(ri, rj, rk);
+                const MeshTriple key = mesh_sorted(ri, rj, rk);
                 uint32_t h = (key.s0 * 0x9E3779B1u) ^ (key.s1 * 0x85EBCA77u) ^ (key.s2 * 0xC2B2AE3Du);
                 h ^= h >> 15;
                 h *= 0x2C1B3C6Du;
@@ -345,7 +281,7 @@ __global__ __launch_bounds__(DEC_WG) void dec_insert_kernel(DgsMeshDecimateArgs 
                         break;
                     }
                     const int32_t* o = a.faces + 3 * (size_t)old;         // a face that was inserted: valid, not degenerate
-                    const DecTriple theirs = dec_sorted(ws.vrank[o[0]], ws.vrank[o[1]], ws.vrank[o[2]]);
+                    const MeshTriple theirs = mesh_sorted(ws.vrank[o[0]], ws.vrank[o[1]], ws.vrank[o[2]]);
                     if (theirs.s0 == key.s0 && theirs.s1 == key.s1 && theirs.s2 == key.s2) {
                         if (f < old) atomicMin(ws.table + slot, f);
                         mine = slot;
@@ -406,9 +342,9 @@ __global__ __launch_bounds__(1024) void dec_sums_kernel(DgsMeshDecimateArgs a, D
         if (threadIdx.x < 5) a.counts[threadIdx.x] = threadIdx.x == 2 ? F - invalid : threadIdx.x == 4 ? invalid : 0u;
         return;
     }
-    const uint32_t nv = dec_scan_blocks(ws.ublk, ws.kblocks, scratch);
-    const uint32_t nf = dec_scan_blocks(ws.fblk, ws.fblocks, scratch);
-    const uint32_t live = dec_scan_blocks(ws.lblk, ws.fblocks, scratch);
+    const uint32_t nv = mesh_scan_blocks(ws.ublk, ws.kblocks, scratch);
+    const uint32_t nf = mesh_scan_blocks(ws.fblk, ws.fblocks, scratch);
+    const uint32_t live = mesh_scan_blocks(ws.lblk, ws.fblocks, scratch);
     if (threadIdx.x == 0) {
         const uint32_t degenerate = F - invalid - live;
         a.counts[0] = nv;

@@ -21,9 +21,8 @@
 //                         border and manifold, summed over the wave and the workgroup in LDS, at most three atomics a workgroup.
 //   rep_fan_kernel        thread = face: the surviving best face of an edge whose second face survives too (the census: an edge of
 //                         incidence exactly 2) unites its corner at a with the other face's corner at a, and the same at b, in a
-//                         lock-free union-find over the corner ids: mesh_clean.hip's (a root is hooked under a SMALLER root with one
-//                         atomicCAS on its own word, path halving only lowers a parent, nothing waits; every access to parent[] in this
-//                         launch is an agent-scope atomic, the XCDs' L2s not being coherent for plain loads inside a launch).
+//                         lock-free union-find over the corner ids (csrc/mesh_common.h, mesh_union: nothing waits, and every access to
+//                         parent[] in this launch is an agent-scope atomic).
 //   rep_flatten_kernel    thread = corner, the next launch (plain loads see the final links): lab[c] = the root of c = its fan's label.
 //                         A root takes atomicMin(vmin[vertex], c): one atomic a FAN, not one a corner -- the closed fan of 16,385 faces
 //                         on one vertex is one atomic on that vertex's word, 300 tetrahedra on one vertex are 300.
@@ -49,6 +48,7 @@
 
 #include "dgs_device.h"
 #include "dgs_mesh_repair.h"
+#include "mesh_common.h"
 
 namespace dgs {
 
@@ -79,8 +79,7 @@ struct RepWs {
     uint32_t* cblk;                                  // [cblocks] totals (then scanned)
     int64_t eslots, dslots, vblocks, fblocks, cblocks, zero_bytes, ones_bytes, bytes;
     __host__ RepWs(void* base, int64_t V, int64_t F) {
-        uintptr_t at = reinterpret_cast<uintptr_t>(base);                // base == nullptr: only the sizes are used
-        auto take = [&at](int64_t words) { const uintptr_t p = at; at += (uintptr_t)((4 * words + 15) & ~(int64_t)15); return reinterpret_cast<uint32_t*>(p); };
+        MeshCarver c(base);                                              // base == nullptr: only the sizes are used
         dslots = 64;
         while (dslots < 2 * F) dslots *= 2;
         eslots = 64;
@@ -88,66 +87,33 @@ struct RepWs {
         vblocks = (V + REP_WG - 1) / REP_WG;
         fblocks = (F + REP_WG - 1) / REP_WG;
         cblocks = (3 * F + REP_WG - 1) / REP_WG;
-        misc = take(REP_MISC_WORDS);                                     // misc ... nm: zeroed by one memset
-        ecount = take(eslots);
-        ebest = reinterpret_cast<rep_u64*>(take(2 * eslots));
-        esecond = reinterpret_cast<rep_u64*>(take(2 * eslots));
-        nm = take(V);
-        zero_bytes = (int64_t)(at - reinterpret_cast<uintptr_t>(base));
-        ekey = reinterpret_cast<rep_u64*>(take(2 * eslots));             // ekey ... vmin: set to 0xff by one memset
-        dtable = take(dslots);
-        vmin = take(V);
-        ones_bytes = (int64_t)(at - reinterpret_cast<uintptr_t>(base)) - zero_bytes;
-        fst = take(F);
-        fslot = take(F);
-        foff = take(F);
-        eslot = take(3 * F);
-        parent = take(3 * F);
-        lab = take(3 * F);
-        coff = take(3 * F);
-        voff = take(V);
-        vblk = take(vblocks);
-        vnm = take(vblocks);
-        fblk = take(fblocks);
-        fdup = take(fblocks);
-        fmark = take(fblocks);
-        cblk = take(cblocks);
-        bytes = (int64_t)(at - reinterpret_cast<uintptr_t>(base));
+        misc = c.take<uint32_t>(REP_MISC_WORDS);                         // misc ... nm: zeroed by one memset
+        ecount = c.take<uint32_t>(eslots);
+        ebest = c.take<rep_u64>(eslots);
+        esecond = c.take<rep_u64>(eslots);
+        nm = c.take<uint32_t>(V);
+        zero_bytes = c.used();
+        ekey = c.take<rep_u64>(eslots);                                  // ekey ... vmin: set to 0xff by one memset
+        dtable = c.take<uint32_t>(dslots);
+        vmin = c.take<uint32_t>(V);
+        ones_bytes = c.used() - zero_bytes;
+        fst = c.take<uint32_t>(F);
+        fslot = c.take<uint32_t>(F);
+        foff = c.take<uint32_t>(F);
+        eslot = c.take<uint32_t>(3 * F);
+        parent = c.take<uint32_t>(3 * F);
+        lab = c.take<uint32_t>(3 * F);
+        coff = c.take<uint32_t>(3 * F);
+        voff = c.take<uint32_t>(V);
+        vblk = c.take<uint32_t>(vblocks);
+        vnm = c.take<uint32_t>(vblocks);
+        fblk = c.take<uint32_t>(fblocks);
+        fdup = c.take<uint32_t>(fblocks);
+        fmark = c.take<uint32_t>(fblocks);
+        cblk = c.take<uint32_t>(cblocks);
+        bytes = c.used();
     }
 };
-
-__device__ __forceinline__ bool rep_valid(int a, int b, int c, uint32_t V) { return (uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V; }
-
-// A relaxed agent-scope atomic load: the value in memory, not a line this XCD's L2 may still hold from before another XCD's atomic.
-__device__ __forceinline__ uint32_t rep_load(uint32_t* p) {
-#ifdef HIPEMU
-    return *p;
-#else
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
-
-// ---- union-find over the corner ids (csrc/mesh_clean.hip); every access to parent[] is an agent-scope atomic ----
-__device__ __forceinline__ uint32_t rep_find(uint32_t* parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = rep_load(parent + x);
-        if (p == x) return x;
-        const uint32_t g = rep_load(parent + p);
-        if (g == p) return p;
-        atomicMin(parent + x, g);
-        x = g;
-    }
-}
-
-__device__ __forceinline__ void rep_union(uint32_t* parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = rep_find(parent, a);
-        b = rep_find(parent, b);
-        if (a == b) return;
-        const uint32_t big = a > b ? a : b, small = a > b ? b : a;
-        if (atomicCAS(parent + big, big, small) == big) return;          // `big` was still a root: hooked.  Otherwise someone hooked it first: again
-    }
-}
 
 // The header's area2, five roundings a component of the normal and five more: every operand converted from a per-lane load.
 __device__ __forceinline__ double rep_area2(const float* vertices, int i, int j, int k) {
@@ -159,21 +125,10 @@ __device__ __forceinline__ double rep_area2(const float* vertices, int i, int j,
     return (nx * nx + ny * ny) + nz * nz;
 }
 
-struct RepTriple {
-    uint32_t s0, s1, s2;                                                  // ascending
-};
-__device__ __forceinline__ RepTriple rep_sorted(uint32_t x, uint32_t y, uint32_t z) {
-    uint32_t t;
-    if (x > y) { t = x; x = y; y = t; }
-    if (y > z) { t = y; y = z; z = t; }
-    if (x > y) { t = x; x = y; y = t; }
-    return {x, y, z};
-}
-
 // The slot of face f (valid, three distinct indices) in the duplicate table, REP_NONE when the probe found none.  The slots a triple
 // passes are taken for good, so all faces of one triple end in one slot, which finally holds their smallest index.
 __device__ __forceinline__ uint32_t rep_dup_slot(const int32_t* faces, const RepWs& ws, uint32_t f, int i, int j, int k) {
-    const RepTriple key = rep_sorted((uint32_t)i, (uint32_t)j, (uint32_t)k);
+    const MeshTriple key = mesh_sorted((uint32_t)i, (uint32_t)j, (uint32_t)k);
     const uint32_t mask = (uint32_t)(ws.dslots - 1);
     uint32_t h = (key.s0 * 0x9E3779B1u) ^ (key.s1 * 0x85EBCA77u) ^ (key.s2 * 0xC2B2AE3Du);
     h ^= h >> 15;
@@ -184,7 +139,7 @@ __device__ __forceinline__ uint32_t rep_dup_slot(const int32_t* faces, const Rep
         const uint32_t old = atomicCAS(ws.dtable + slot, REP_NONE, f);
         if (old == REP_NONE) return slot;
         const int32_t* o = faces + 3 * (size_t)old;                       // a face that was inserted: valid, three distinct indices
-        const RepTriple theirs = rep_sorted((uint32_t)o[0], (uint32_t)o[1], (uint32_t)o[2]);
+        const MeshTriple theirs = mesh_sorted((uint32_t)o[0], (uint32_t)o[1], (uint32_t)o[2]);
         if (theirs.s0 == key.s0 && theirs.s1 == key.s1 && theirs.s2 == key.s2) {
             if (f < old) atomicMin(ws.dtable + slot, f);
             return slot;
@@ -224,7 +179,7 @@ __global__ __launch_bounds__(REP_WG) void rep_face_kernel(DgsMeshRepairArgs a, R
         const int32_t* t = a.faces + 3 * (size_t)f;
         const int i = t[0], j = t[1], k = t[2];
         uint32_t st = REP_DEAD, slot = REP_NONE;
-        if (!rep_valid(i, j, k, V)) {
+        if (!mesh_face_valid(i, j, k, V)) {
             invalid = true;
         } else if (i == j || i == k || j == k) {
             null = true;
@@ -355,8 +310,8 @@ __global__ __launch_bounds__(REP_WG) void rep_fan_kernel(DgsMeshRepairArgs a, Re
         const int32_t* o = a.faces + 3 * (size_t)g;
         const int va = v[k], vb = v[(k + 1) % 3];
         const uint32_t ja = o[0] == va ? 0u : (o[1] == va ? 1u : 2u), jb = o[0] == vb ? 0u : (o[1] == vb ? 1u : 2u);
-        rep_union(ws.parent, 3 * f + (uint32_t)k, 3 * g + ja);
-        rep_union(ws.parent, 3 * f + (uint32_t)((k + 1) % 3), 3 * g + jb);
+        mesh_union(ws.parent, 3 * f + (uint32_t)k, 3 * g + ja);
+        mesh_union(ws.parent, 3 * f + (uint32_t)((k + 1) % 3), 3 * g + jb);
     }
 }
 
@@ -413,22 +368,6 @@ __global__ __launch_bounds__(REP_WG) void rep_fscan_kernel(DgsMeshRepairArgs a, 
     }
 }
 
-// Exclusive scan of n block totals in place by one workgroup of 1,024 (the form of clean_scan_blocks): a contiguous piece a thread, as
-// long as it has to be, and a scan of the pieces' sums -> the sum of all.
-__device__ __forceinline__ uint32_t rep_scan_blocks(uint32_t* blk, int64_t n, uint32_t* scratch) {
-    const int64_t per = (n + 1023) / 1024, c0 = per * threadIdx.x, c1 = c0 + per < n ? c0 + per : n;
-    uint32_t s = 0;
-    for (int64_t c = c0; c < c1; ++c) s += blk[c];
-    uint32_t total;
-    uint32_t run = block_exclusive_scan<1024>(s, scratch, &total);
-    for (int64_t c = c0; c < c1; ++c) {
-        const uint32_t here = blk[c];
-        blk[c] = run;
-        run += here;
-    }
-    return total;
-}
-
 __device__ __forceinline__ uint32_t rep_sum_blocks(const uint32_t* blk, int64_t n, uint32_t* scratch) {
     uint32_t s = 0, total;
     for (int64_t c = threadIdx.x; c < n; c += 1024) s += blk[c];
@@ -444,9 +383,9 @@ __global__ __launch_bounds__(1024) void rep_sums_kernel(DgsMeshRepairArgs a, Rep
         if (CENSUS && threadIdx.x < DGS_MESH_TOPOLOGY_COUNTS) a.topology[threadIdx.x] = -1;
         return;
     }
-    const uint32_t nv = rep_scan_blocks(ws.vblk, ws.vblocks, scratch);
-    const uint32_t added = rep_scan_blocks(ws.cblk, ws.cblocks, scratch);
-    const uint32_t nf = rep_scan_blocks(ws.fblk, ws.fblocks, scratch);
+    const uint32_t nv = mesh_scan_blocks(ws.vblk, ws.vblocks, scratch);
+    const uint32_t added = mesh_scan_blocks(ws.cblk, ws.cblocks, scratch);
+    const uint32_t nf = mesh_scan_blocks(ws.fblk, ws.fblocks, scratch);
     const uint32_t vnm = rep_sum_blocks(ws.vnm, ws.vblocks, scratch);
     const uint32_t dup = rep_sum_blocks(ws.fdup, ws.fblocks, scratch);
     const uint32_t marked = rep_sum_blocks(ws.fmark, ws.fblocks, scratch);
@@ -481,20 +420,11 @@ __global__ void rep_nothing_kernel(uint32_t* counts, int64_t* topology, uint32_t
     if (topology && threadIdx.x < DGS_MESH_TOPOLOGY_COUNTS) topology[threadIdx.x] = 0;
 }
 
-// The 12 bytes, not three floats: NaN payloads stay.
-__device__ __forceinline__ void rep_copy_vertex(const DgsMeshRepairArgs& a, uint32_t v, uint32_t at) {
-    const uint32_t* in = reinterpret_cast<const uint32_t*>(a.vertices) + 3 * (size_t)v;
-    uint32_t* out = reinterpret_cast<uint32_t*>(a.out_vertices) + 3 * (size_t)at;
-    out[0] = in[0];
-    out[1] = in[1];
-    out[2] = in[2];
-}
-
 __global__ __launch_bounds__(REP_WG) void rep_emit_vertices_kernel(DgsMeshRepairArgs a, RepWs ws) {
     const uint32_t v = blockIdx.x * REP_WG + threadIdx.x;
     if (ws.misc[REP_ERROR] || v >= (uint32_t)a.V || ws.vmin[v] == REP_NONE) return;
     const uint32_t at = ws.vblk[blockIdx.x] + ws.voff[v];
-    if ((int64_t)at < a.max_vertices) rep_copy_vertex(a, v, at);
+    if ((int64_t)at < a.max_vertices) mesh_copy_vertex_bytes(a.vertices, v, a.out_vertices, at);
 }
 
 __global__ __launch_bounds__(REP_WG) void rep_emit_faces_kernel(DgsMeshRepairArgs a, RepWs ws) {
@@ -510,7 +440,7 @@ __global__ __launch_bounds__(REP_WG) void rep_emit_faces_kernel(DgsMeshRepairArg
             row[k] = ws.vblk[v / REP_WG] + ws.voff[v];
         } else {
             row[k] = vref + ws.cblk[r / REP_WG] + ws.coff[r];
-            if (r == c && (int64_t)row[k] < a.max_vertices) rep_copy_vertex(a, v, row[k]);   // the fan's root writes the fan's copy
+            if (r == c && (int64_t)row[k] < a.max_vertices) mesh_copy_vertex_bytes(a.vertices, v, a.out_vertices, row[k]);   // the fan's root writes the fan's copy
         }
     }
     if ((int64_t)at >= a.max_faces) return;

@@ -38,6 +38,7 @@
 
 #include "dgs_device.h"
 #include "dgs_mesh_smooth.h"
+#include "mesh_common.h"
 
 namespace dgs {
 
@@ -62,24 +63,21 @@ struct SmWs {
     int32_t* nbr;                                     // [6 F] the segments
     int64_t vblocks, fblocks, zero_bytes, bytes;
     __host__ SmWs(void* base, int64_t V, int64_t F) {
-        uintptr_t at = reinterpret_cast<uintptr_t>(base);                // base == nullptr: only the sizes are used
-        auto take = [&at](int64_t words) { const uintptr_t p = at; at += (uintptr_t)((4 * words + 15) & ~(int64_t)15); return reinterpret_cast<uint32_t*>(p); };
+        MeshCarver c(base);                                              // base == nullptr: only the sizes are used
         vblocks = (V + SM_WG - 1) / SM_WG;
         fblocks = (F + SM_WG - 1) / SM_WG;
-        misc = take(SM_MISC_WORDS);                                      // misc, cnt, cursor: zeroed by the call's one memset
-        cnt = take(V);
-        cursor = take(V);
-        zero_bytes = (int64_t)(at - reinterpret_cast<uintptr_t>(base));
-        start = take(V);
-        blk = take(vblocks);
-        flg = take(vblocks);
-        tmp = reinterpret_cast<float*>(take(3 * V));
-        nbr = reinterpret_cast<int32_t*>(take(6 * F));
-        bytes = (int64_t)(at - reinterpret_cast<uintptr_t>(base));
+        misc = c.take<uint32_t>(SM_MISC_WORDS);                          // misc, cnt, cursor: zeroed by the call's one memset
+        cnt = c.take<uint32_t>(V);
+        cursor = c.take<uint32_t>(V);
+        zero_bytes = c.used();
+        start = c.take<uint32_t>(V);
+        blk = c.take<uint32_t>(vblocks);
+        flg = c.take<uint32_t>(vblocks);
+        tmp = c.take<float>(3 * V);
+        nbr = c.take<int32_t>(6 * F);
+        bytes = c.used();
     }
 };
-
-__device__ __forceinline__ bool sm_valid(int a, int b, int c, uint32_t V) { return (uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V; }
 
 __device__ __forceinline__ bool sm_moving(uint32_t c, const uint8_t* fixed, uint32_t v) {
     return c >= 1 && c <= SM_CAP && (fixed == nullptr || fixed[v] == 0);
@@ -110,7 +108,7 @@ __global__ __launch_bounds__(SM_WG) void sm_count_kernel(DgsMeshSmoothArgs a, Sm
     if (f < (uint32_t)a.F) {
         const int32_t* in = a.faces + 3 * (size_t)f;
         const int i = in[0], j = in[1], k = in[2];
-        invalid = !sm_valid(i, j, k, V);
+        invalid = !mesh_face_valid(i, j, k, V);
         null = !invalid && (i == j || i == k || j == k);
         live = !invalid && !null;
         t[0] = (uint32_t)i;
@@ -140,7 +138,7 @@ __global__ __launch_bounds__(SM_WG) void sm_scan_kernel(DgsMeshSmoothArgs a, SmW
     }
 }
 
-// Exclusive scan of the block totals in place by one workgroup of 1,024 (the form of dec_scan_blocks), the packed flags added up, the
+// Exclusive scan of the block totals in place by one workgroup of 1,024 (the form of mesh_scan_blocks, csrc/mesh_common.h), the packed flags added up, the
 // counts to the caller.
 __global__ __launch_bounds__(1024) void sm_sums_kernel(DgsMeshSmoothArgs a, SmWs ws) {
     __shared__ uint32_t scratch[1024 / DGS_WAVE + 1];
@@ -175,7 +173,7 @@ __global__ __launch_bounds__(SM_WG) void sm_fill_kernel(DgsMeshSmoothArgs a, SmW
     if (f < (uint32_t)a.F) {
         const int32_t* in = a.faces + 3 * (size_t)f;
         const int i = in[0], j = in[1], k = in[2];
-        live = sm_valid(i, j, k, V) && i != j && i != k && j != k;
+        live = mesh_face_valid(i, j, k, V) && i != j && i != k && j != k;
         t[0] = (uint32_t)i;
         t[1] = (uint32_t)j;
         t[2] = (uint32_t)k;

@@ -253,6 +253,59 @@ class Mesh:
         return f"Mesh(vertices={tuple(self.vertices.shape)}, faces={tuple(self.faces.shape)}, device={self.vertices.device})"
 
 
+def _check_rc(L, rc, name):
+    """The return code of a C call: -1 (an invalid argument) is a ValueError, every other failure a RuntimeError."""
+    if rc != 0:
+        from . import _native
+        raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed: {rc} ({_native.status_string(L, rc)})")
+
+
+def _check_mesh(who, vertices, faces):
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise ValueError(f"{who}: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{who}: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+    if faces.device != vertices.device:
+        raise ValueError(f"{who}: vertices on {vertices.device}, faces on {faces.device}")
+
+
+class _MeshCall:
+    """What the C calls of one mesh stage need: the checked, detached, contiguous mesh, the library, a workspace, the current stream and
+    the stage's argument block `a` with V, F, vertices, faces, workspace and workspace_bytes filled in.  `symbols` and `feature` are
+    for a library that predates the stage, `args` is the type of the block, `size(L, a)` the workspace size and `limit` says what
+    sizes the stage takes.  A caller with parameters of its own calls _check_mesh first, so that the mesh is complained about first."""
+
+    def __init__(self, who, vertices, faces, lib, symbols, feature, args, size, limit):
+        from . import _native
+        _check_mesh(who, vertices, faces)
+        self.who, self._native = who, _native
+        self.L = L = lib or _native.lib()
+        if not all(hasattr(L, name) for name in symbols):
+            raise RuntimeError(f"{who}: this build of the library predates {feature} -- rebuild it (`python -m dgs_amd.build`)")
+        self.vertices, self.faces = vertices.detach().contiguous(), faces.detach().contiguous()
+        self.dev = vertices.device
+        self.a = a = args()
+        a.V, a.F = self.vertices.shape[0], self.faces.shape[0]
+        a.workspace_bytes = size(L, a)
+        if a.workspace_bytes <= 0:
+            raise ValueError(f"{who}: unsupported size V = {a.V}, F = {a.F} ({limit})")
+        self.ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=self.dev)
+        a.workspace = ctypes.c_void_p(self.ws.data_ptr())
+        a.vertices = ctypes.c_void_p(self.vertices.data_ptr()) if a.V else None
+        a.faces = ctypes.c_void_p(self.faces.data_ptr()) if a.F else None
+        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream) if vertices.is_cuda else None
+
+    def call(self, name):
+        _check_rc(self.L, getattr(self.L, name)(ctypes.byref(self.a), self.stream), name)
+
+    def done(self, *more):
+        """After the last call: the mesh, the workspace and `more` (a None among them is skipped) are in use on the current stream."""
+        if self.vertices.is_cuda:
+            for t in (self.vertices, self.faces, self.ws) + more:
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream(self.dev))
+
+
 def marching_cubes(occ, level, lib=None):
     """The counterpart of `mcubes.marching_cubes(occ, level)` on occ's device: occ float32 [X, Y, Z] -> (vertices float32 [V, 3] in
     index coordinates, triangles int32 [F, 3]), in the canonical order of include/dgs_mesh.h (csrc/mesh.hip); a sample is inside iff
@@ -275,19 +328,14 @@ def marching_cubes(occ, level, lib=None):
         counts = torch.empty(2, dtype=torch.int32, device=dev)              # the call writes uint32 [2]
         a.occ, a.counts, a.workspace = (ctypes.c_void_p(t.data_ptr()) for t in (occ, counts, ws))
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if occ.is_cuda else None
-
-        def check(rc, name):
-            if rc != 0:
-                raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed: {rc} ({_native.status_string(L, rc)})")
-
-        check(L.dgs_marching_cubes_count(ctypes.byref(a), stream), "dgs_marching_cubes_count")
+        _check_rc(L, L.dgs_marching_cubes_count(ctypes.byref(a), stream), "dgs_marching_cubes_count")
         nv, nf = (c & 0xFFFFFFFF for c in counts.tolist())                  # the feature's one host synchronisation
         vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         triangles = torch.empty((nf, 3), dtype=torch.int32, device=dev)
         if nv:
             a.vertices, a.triangles = ctypes.c_void_p(vertices.data_ptr()), ctypes.c_void_p(triangles.data_ptr())
             a.max_vertices, a.max_triangles = nv, nf
-            check(L.dgs_marching_cubes_emit(ctypes.byref(a), stream), "dgs_marching_cubes_emit")
+            _check_rc(L, L.dgs_marching_cubes_emit(ctypes.byref(a), stream), "dgs_marching_cubes_emit")
         if occ.is_cuda:
             for t in (occ, ws, counts):
                 t.record_stream(torch.cuda.current_stream(dev))
@@ -302,38 +350,17 @@ def remove_small_components(vertices, faces, min_f=64, min_d=20, return_labels=F
     return_labels also labels int32 [F], the smallest vertex index of each input face's component (-1: an index outside [0, V)).
     dgs_mesh_clean_count, ONE readback of the five counts to size the outputs, dgs_mesh_clean_emit."""
     from . import _native
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise ValueError(f"remove_small_components: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
-        raise ValueError(f"remove_small_components: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
-    if faces.device != vertices.device:
-        raise ValueError(f"remove_small_components: vertices on {vertices.device}, faces on {faces.device}")
+    _check_mesh("remove_small_components", vertices, faces)
     if int(min_f) != min_f or min_f < 0 or not min_d >= 0:
         raise ValueError(f"remove_small_components: min_f must be an integer >= 0 and min_d a percentage >= 0, got {min_f}, {min_d}")
     with torch.no_grad():
-        vertices, faces = vertices.detach().contiguous(), faces.detach().contiguous()
-        dev = vertices.device
-        L = lib or _native.lib()
-        if not all(hasattr(L, name) for name in _native.MESH_CLEAN_SYMBOLS):
-            raise RuntimeError("remove_small_components: this build of the library predates the mesh clean-up -- rebuild it (`python -m dgs_amd.build`)")
-        a = _native.DgsMeshCleanArgs()
-        a.V, a.F = vertices.shape[0], faces.shape[0]
+        m = _MeshCall("remove_small_components", vertices, faces, lib, _native.MESH_CLEAN_SYMBOLS, "the mesh clean-up", _native.DgsMeshCleanArgs,
+                      lambda L, a: L.dgs_mesh_clean_workspace_bytes(a.V, a.F), "at most 2^30 each")
+        a, dev = m.a, m.dev
         a.min_faces, a.min_diag_pct = int(min_f), float(min_d)
-        a.workspace_bytes = L.dgs_mesh_clean_workspace_bytes(a.V, a.F)
-        if a.workspace_bytes <= 0:
-            raise ValueError(f"remove_small_components: unsupported size V = {a.V}, F = {a.F} (at most 2^30 each)")
-        ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=dev)
         counts = torch.empty(5, dtype=torch.int32, device=dev)              # the call writes uint32 [5]
-        a.counts, a.workspace = ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(ws.data_ptr())
-        a.vertices = ctypes.c_void_p(vertices.data_ptr()) if a.V else None
-        a.faces = ctypes.c_void_p(faces.data_ptr()) if a.F else None
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if vertices.is_cuda else None
-
-        def check(rc, name):
-            if rc != 0:
-                raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed: {rc} ({_native.status_string(L, rc)})")
-
-        check(L.dgs_mesh_clean_count(ctypes.byref(a), stream), "dgs_mesh_clean_count")
+        a.counts = ctypes.c_void_p(counts.data_ptr())
+        m.call("dgs_mesh_clean_count")
         nv, nf = (c & 0xFFFFFFFF for c in counts.tolist()[:2])              # the feature's one host synchronisation
         out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         out_f = torch.empty((nf, 3), dtype=torch.int32, device=dev)
@@ -343,54 +370,31 @@ def remove_small_components(vertices, faces, min_f=64, min_d=20, return_labels=F
             a.out_faces = ctypes.c_void_p(out_f.data_ptr()) if nf else None
             a.labels = ctypes.c_void_p(labels.data_ptr()) if return_labels else None
             a.max_vertices, a.max_faces = nv, nf
-            check(L.dgs_mesh_clean_emit(ctypes.byref(a), stream), "dgs_mesh_clean_emit")
-        if vertices.is_cuda:
-            for t in (vertices, faces, ws, counts):
-                t.record_stream(torch.cuda.current_stream(dev))
+            m.call("dgs_mesh_clean_emit")
+        m.done(counts)
     return (out_v, out_f, labels) if return_labels else (out_v, out_f)
 
 
-class _Clustering:
+class _Clustering(_MeshCall):
     """The mesh, the library and one workspace large enough for every n up to n_max: count(n) as often as the caller likes (one
     readback of the five counts each), then emit() at the n counted last."""
 
     def __init__(self, vertices, faces, n_max, lib, who):
         from . import _native
-        if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-            raise ValueError(f"{who}: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
-        if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
-            raise ValueError(f"{who}: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
-        if faces.device != vertices.device:
-            raise ValueError(f"{who}: vertices on {vertices.device}, faces on {faces.device}")
+        _check_mesh(who, vertices, faces)
         if int(n_max) != n_max or not 1 <= n_max <= 1024:
             raise ValueError(f"{who}: the grid must have an integer number of cells per axis in [1, 1024], got {n_max}")
-        self.who, self._native = who, _native
-        self.vertices, self.faces = vertices.detach().contiguous(), faces.detach().contiguous()
-        self.dev = vertices.device
-        self.L = L = lib or _native.lib()
-        if not all(hasattr(L, name) for name in _native.MESH_DECIMATE_SYMBOLS):
-            raise RuntimeError(f"{who}: this build of the library predates the mesh decimation -- rebuild it (`python -m dgs_amd.build`)")
-        self.a = a = _native.DgsMeshDecimateArgs()
-        a.V, a.F = self.vertices.shape[0], self.faces.shape[0]
-        a.workspace_bytes = L.dgs_mesh_decimate_workspace_bytes(a.V, a.F, int(n_max))       # grows with n: enough for every n <= n_max
-        if a.workspace_bytes <= 0:
-            raise ValueError(f"{who}: unsupported size V = {a.V}, F = {a.F} (at most 2^30 each)")
-        self.ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=self.dev)
+        super().__init__(who, vertices, faces, lib, _native.MESH_DECIMATE_SYMBOLS, "the mesh decimation", _native.DgsMeshDecimateArgs,
+                         lambda L, a: L.dgs_mesh_decimate_workspace_bytes(a.V, a.F, int(n_max)),    # grows with n: enough for every n <= n_max
+                         "at most 2^30 each")
         self.counts_dev = torch.empty(5, dtype=torch.int32, device=self.dev)  # the call writes uint32 [5]
-        a.counts, a.workspace = ctypes.c_void_p(self.counts_dev.data_ptr()), ctypes.c_void_p(self.ws.data_ptr())
-        a.vertices = ctypes.c_void_p(self.vertices.data_ptr()) if a.V else None
-        a.faces = ctypes.c_void_p(self.faces.data_ptr()) if a.F else None
-        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream) if vertices.is_cuda else None
+        self.a.counts = ctypes.c_void_p(self.counts_dev.data_ptr())
         self.counts = None
-
-    def _check(self, rc, name):
-        if rc != 0:
-            raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed: {rc} ({self._native.status_string(self.L, rc)})")
 
     def count(self, n):
         """-> [V', F', degenerate, duplicates dropped, invalid] at n cells per axis; a host synchronisation."""
         self.a.n = int(n)
-        self._check(self.L.dgs_mesh_decimate_count(ctypes.byref(self.a), self.stream), "dgs_mesh_decimate_count")
+        self.call("dgs_mesh_decimate_count")
         self.counts = [c & 0xFFFFFFFF for c in self.counts_dev.tolist()]
         if self.counts[0] == 0xFFFFFFFF:
             raise RuntimeError(f"{self.who}: dgs_mesh_decimate_count found no slot for a face in its table")
@@ -404,10 +408,8 @@ class _Clustering:
             a = self.a
             a.out_vertices, a.out_faces = ctypes.c_void_p(out_v.data_ptr()), ctypes.c_void_p(out_f.data_ptr())
             a.max_vertices, a.max_faces = nv, nf
-            self._check(self.L.dgs_mesh_decimate_emit(ctypes.byref(a), self.stream), "dgs_mesh_decimate_emit")
-        if self.vertices.is_cuda:
-            for t in (self.vertices, self.faces, self.ws, self.counts_dev):
-                t.record_stream(torch.cuda.current_stream(self.dev))
+            self.call("dgs_mesh_decimate_emit")
+        self.done(self.counts_dev)
         return out_v, out_f
 
 
@@ -466,12 +468,7 @@ def smooth_mesh(vertices, faces, iterations=10, lam=0.5, mu=-0.53, fixed=None, r
     call's only host synchronisation.  The same input gives the same bytes.  Not part of this: border handling (an open mesh shrinks
     at its border), cotangent weights, remeshing, non-manifold repair (repair_mesh, before this).  One C call on the current stream."""
     from . import _native
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise ValueError(f"smooth_mesh: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
-        raise ValueError(f"smooth_mesh: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
-    if faces.device != vertices.device:
-        raise ValueError(f"smooth_mesh: vertices on {vertices.device}, faces on {faces.device}")
+    _check_mesh("smooth_mesh", vertices, faces)
     if int(iterations) != iterations or not 0 <= iterations <= 1 << 20:
         raise ValueError(f"smooth_mesh: iterations must be an integer in [0, 2^20], got {iterations}")
     if not (math.isfinite(lam) and math.isfinite(mu)):
@@ -482,75 +479,28 @@ def smooth_mesh(vertices, faces, iterations=10, lam=0.5, mu=-0.53, fixed=None, r
         if fixed.device != vertices.device:
             raise ValueError(f"smooth_mesh: vertices on {vertices.device}, fixed on {fixed.device}")
     with torch.no_grad():
-        L = lib or _native.lib()
-        if not all(hasattr(L, name) for name in _native.MESH_SMOOTH_SYMBOLS):
-            raise RuntimeError("smooth_mesh: this build of the library predates the mesh smoothing -- rebuild it (`python -m dgs_amd.build`)")
-        dev = vertices.device
-        vertices, faces = vertices.detach().contiguous(), faces.detach().contiguous()
+        m = _MeshCall("smooth_mesh", vertices, faces, lib, _native.MESH_SMOOTH_SYMBOLS, "the mesh smoothing", _native.DgsMeshSmoothArgs,
+                      lambda L, a: L.dgs_mesh_smooth_workspace_bytes(a.V, a.F), "at most 2^30 and 2^29")
+        a = m.a
         if fixed is not None:
             fixed = fixed.detach().contiguous().view(torch.uint8)           # a bool is one byte, 0 or 1
-        a = _native.DgsMeshSmoothArgs()
-        a.V, a.F = vertices.shape[0], faces.shape[0]
         a.lam, a.mu, a.iterations = float(lam), float(mu), int(iterations)
-        a.workspace_bytes = L.dgs_mesh_smooth_workspace_bytes(a.V, a.F)
-        if a.workspace_bytes <= 0:
-            raise ValueError(f"smooth_mesh: unsupported size V = {a.V}, F = {a.F} (at most 2^30 and 2^29)")
-        ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=dev)
-        out = torch.empty((a.V, 3), dtype=torch.float32, device=dev)
-        counts = torch.empty(4, dtype=torch.int32, device=dev) if return_counts else None   # the call writes uint32 [4]
+        out = torch.empty((a.V, 3), dtype=torch.float32, device=m.dev)
+        counts = torch.empty(4, dtype=torch.int32, device=m.dev) if return_counts else None   # the call writes uint32 [4]
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-        a.vertices, a.faces, a.fixed, a.out_vertices, a.counts = ptr(vertices), ptr(faces), ptr(fixed), ptr(out), ptr(counts)
-        a.workspace = ctypes.c_void_p(ws.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if vertices.is_cuda else None
-        rc = L.dgs_mesh_smooth(ctypes.byref(a), stream)
-        if rc != 0:
-            raise (ValueError if rc == -1 else RuntimeError)(f"dgs_mesh_smooth failed: {rc} ({_native.status_string(L, rc)})")
-        if vertices.is_cuda:
-            for t in (vertices, faces, fixed, ws):
-                if t is not None:
-                    t.record_stream(torch.cuda.current_stream(dev))
+        a.fixed, a.out_vertices, a.counts = ptr(fixed), ptr(out), ptr(counts)
+        m.call("dgs_mesh_smooth")
+        m.done(fixed)
         if return_counts:
             return out, [c & 0xFFFFFFFF for c in counts.tolist()]           # the one host synchronisation
     return out
 
 
-class _Repair:
-    """The checked mesh, the library, a workspace and the argument block of dgs_mesh_repair_count / _emit / dgs_mesh_topology."""
-
-    def __init__(self, vertices, faces, lib, who):
-        from . import _native
-        if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-            raise ValueError(f"{who}: vertices must be float32 [V, 3], got {vertices.dtype} {tuple(vertices.shape)}")
-        if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
-            raise ValueError(f"{who}: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
-        if faces.device != vertices.device:
-            raise ValueError(f"{who}: vertices on {vertices.device}, faces on {faces.device}")
-        self._native = _native
-        self.L = L = lib or _native.lib()
-        if not all(hasattr(L, name) for name in _native.MESH_REPAIR_SYMBOLS):
-            raise RuntimeError(f"{who}: this build of the library predates the mesh repair -- rebuild it (`python -m dgs_amd.build`)")
-        self.vertices, self.faces = vertices.detach().contiguous(), faces.detach().contiguous()
-        self.dev = vertices.device
-        self.a = a = _native.DgsMeshRepairArgs()
-        a.V, a.F = self.vertices.shape[0], self.faces.shape[0]
-        a.workspace_bytes = L.dgs_mesh_repair_workspace_bytes(a.V, a.F)
-        if a.workspace_bytes <= 0:
-            raise ValueError(f"{who}: unsupported size V = {a.V}, F = {a.F} (at most 2^30 and 2^28)")
-        self.ws = torch.empty(a.workspace_bytes, dtype=torch.uint8, device=self.dev)
-        a.workspace = ctypes.c_void_p(self.ws.data_ptr())
-        a.vertices = ctypes.c_void_p(self.vertices.data_ptr()) if a.V else None
-        a.faces = ctypes.c_void_p(self.faces.data_ptr()) if a.F else None
-        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream) if vertices.is_cuda else None
-
-    def call(self, name):
-        rc = getattr(self.L, name)(ctypes.byref(self.a), self.stream)
-        if rc != 0:
-            raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed: {rc} ({self._native.status_string(self.L, rc)})")
-
-    def done(self, *more):
-        if self.vertices.is_cuda:
-            for t in (self.vertices, self.faces, self.ws) + more:
-                t.record_stream(torch.cuda.current_stream(self.dev))
+def _repair_call(vertices, faces, lib, who):
+    """The _MeshCall of dgs_mesh_repair_count / _emit / dgs_mesh_topology."""
+    from . import _native
+    return _MeshCall(who, vertices, faces, lib, _native.MESH_REPAIR_SYMBOLS, "the mesh repair", _native.DgsMeshRepairArgs,
+                     lambda L, a: L.dgs_mesh_repair_workspace_bytes(a.V, a.F), "at most 2^30 and 2^28")
 
 
 def repair_mesh(vertices, faces, return_counts=False, lib=None):
@@ -567,7 +517,7 @@ def repair_mesh(vertices, faces, return_counts=False, lib=None):
     gives the same bytes.  Orientation is neither checked nor repaired; an edge that kept a face which another edge removed becomes a
     border.  dgs_mesh_repair_count, ONE readback of the ten counts to size the outputs, dgs_mesh_repair_emit."""
     with torch.no_grad():
-        r = _Repair(vertices, faces, lib, "repair_mesh")
+        r = _repair_call(vertices, faces, lib, "repair_mesh")
         counts_dev = torch.empty(len(r._native.MESH_REPAIR_COUNTS), dtype=torch.int32, device=r.dev)   # the call writes uint32 [10]
         r.a.counts = ctypes.c_void_p(counts_dev.data_ptr())
         r.call("dgs_mesh_repair_count")
@@ -593,7 +543,7 @@ def mesh_topology(vertices, faces, lib=None):
     [0, V) and differ; a face that occurs twice counts twice, and the coordinates are not read.  It decides nothing for repair_mesh:
     it is the check of a raw mesh (is a repair needed?) as well as of a repaired one.  One C call and one readback of seven integers."""
     with torch.no_grad():
-        r = _Repair(vertices, faces, lib, "mesh_topology")
+        r = _repair_call(vertices, faces, lib, "mesh_topology")
         out = torch.empty(len(r._native.MESH_TOPOLOGY_COUNTS), dtype=torch.int64, device=r.dev)
         r.a.topology = ctypes.c_void_p(out.data_ptr())
         r.call("dgs_mesh_topology")
@@ -659,9 +609,7 @@ def mesh_attributes(pc, points, num_blocks=64, reach=2, attr=None, want=("colors
         a.xyz, a.scaling, a.rotation, a.opacity, a.attr, a.points, a.workspace = (ptr(t) for t in (xyzs, scaling, rotation, opacity, attr, points, ws))
         a.density, a.attr_out, a.gradient = ptr(density), ptr(colors), ptr(gradient)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if xyz.is_cuda else None
-        rc = L.dgs_mesh_attributes(ctypes.byref(a), stream)
-        if rc != 0:
-            raise (ValueError if rc == -1 else RuntimeError)(f"dgs_mesh_attributes failed: {rc} ({_native.status_string(L, rc)})")
+        _check_rc(L, L.dgs_mesh_attributes(ctypes.byref(a), stream), "dgs_mesh_attributes")
         if xyz.is_cuda:
             for t in (xyzs, scaling, rotation, opacity, attr, points, ws):
                 t.record_stream(torch.cuda.current_stream(dev))

@@ -134,7 +134,7 @@ def main():
                     "census_before": consumers.mesh_topology(v, f), "census_after": consumers.mesh_topology(ov, of),
                     "median_ours_s": statistics.median(x["ours_s"] for x in rows), "median_copy_s": statistics.median(x["copy_s"] for x in rows),
                     "faster_than_the_copy_in_every_pair": all(x["ratio"] > 1 for x in rows), "smallest_ratio": min(x["ratio"] for x in rows),
-                    "workspace_bytes": consumers._Repair(v, f, None, "bench").a.workspace_bytes,
+                    "workspace_bytes": consumers._repair_call(v, f, None, "bench").a.workspace_bytes,
                     "ours_same_bytes_in_every_call": bool(torch.equal(ov.view(torch.int32), again[0].view(torch.int32)) and torch.equal(of, again[1]))}
         print(key, {k: x for k, x in out[key].items() if k != "alternating_pairs"}, flush=True)
     with open(args.out, "w") as f:
